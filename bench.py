@@ -19,6 +19,11 @@ exits non-zero when fewer than N devices are visible; under the driver's torchru
 launch it just joins the group.
 
 Rank 0 prints ONE JSON line (metric = ray-surface intersections/s, whole job).
+A plain run sets up, warms up, times EXACTLY K steps (`ms_per_step` = wall clock of one),
+writes the last step's outputs when `--dump-outputs DIR` is given, and prints the line.
+Everything else it can measure runs only with `--full`: the exchange legs of N > 1, the
+device bandwidth and stream-fill yardsticks, the steady-state legs, the live PMC traffic
+passes and the CPU / reference baselines (their fields are null in a plain run).
 `roofline` refers to the trace kernel in the mode that was run: `frac` is on the bytes
 the launch really moves (== the PMC traffic), `frac_algorithmic` on SURVEY 8d's figure,
 `frac_of_achievable` against a device copy measured in the same run.  `cpu_baseline` is
@@ -129,6 +134,16 @@ def parse_args():
                          "on the host, stock torch backend on the GPU)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--ref-seconds", type=float, default=8.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the exchange legs "
+                         "without / with the other exchange kind (N > 1), device copy and "
+                         "stream-fill bandwidth, the --settle steady-state legs, the live "
+                         "--traffic passes and the CPU / reference baselines.  Off by default: "
+                         "a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its "
+                         "last step as DIR/<name>.npy (float32 / float64; a fixed, seeded "
+                         "sample of the rays when the whole output exceeds the size cap)")
     return ap.parse_args()
 
 
@@ -256,6 +271,31 @@ def make_rays(hip, n, dtype, hy, seed, device, out=None):
     rays = [p.contiguous().clone() for p in planes]
     rays.append(torch.zeros(n, dtype=dtype, device=device))
     return rays
+
+
+DUMP_CAP_BYTES = 48 << 20  # everything --dump-outputs writes, sample index included
+
+
+def dump_outputs(outdir, arrays, n):
+    """`--dump-outputs`: `arrays` = {name: tensor}, the per-ray ones with the ray index as
+    their LAST axis (length n), the rest small (moments).  Every per-ray array is cut to the
+    same fixed, seeded sample of ray indices when all of them together would exceed
+    DUMP_CAP_BYTES (the sample itself is written as `ray_index.npy`)."""
+    os.makedirs(outdir, exist_ok=True)
+    per_ray = {k: v for k, v in arrays.items() if v.dim() and v.shape[-1] == n}
+    bytes_per_ray = sum(v.element_size() * (v.numel() // max(n, 1)) for v in per_ray.values())
+    # (+ 8 bytes per sampled ray: its index)
+    keep = n if bytes_per_ray * n <= DUMP_CAP_BYTES else DUMP_CAP_BYTES // (bytes_per_ray + 8)
+    idx = None
+    if keep < n:
+        idx = np.sort(np.random.default_rng(20240917).choice(n, size=keep, replace=False))
+        np.save(os.path.join(outdir, "ray_index.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        if idx is not None and name in per_ray:
+            t = t.index_select(t.dim() - 1, torch.as_tensor(idx, device=t.device))
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+        np.save(os.path.join(outdir, f"{name}.npy"), a)
 
 
 def cpu_baseline(table, hy, mode, budget_s, wl=0, threads=None):
@@ -723,6 +763,8 @@ def main():
         all_slots = [torch.zeros((world,) + tuple(slots[0].shape), dtype=torch.float64,
                                  device=device) for _ in range(2)]
     step_no = [0]
+    opd_out = [None]  # (opd, intensity, pupil, moments) of the last --mode opd step
+    last_res = [None]  # what the last timed step returned (for --dump-outputs)
 
     def spot_step(ev0=None, ev1=None):
         """Fused pipeline: pupil planes in, seven doubles out (+ the all-reduce of
@@ -737,8 +779,8 @@ def main():
         if ev0 is not None:
             ev0.record()
         if opd_mode:
-            hip.trace_opd(opd_params, px, py, wl, field=(0.0, hy), want_pupil=True,
-                          moments=mom[k], check_status=False)
+            opd_out[0] = hip.trace_opd(opd_params, px, py, wl, field=(0.0, hy), want_pupil=True,
+                                       moments=mom[k], check_status=False)
         else:
             hip.trace_spot(px, py, wl, field=(0.0, hy), out=mom[k], check_status=False)
         if ev1 is not None:
@@ -819,7 +861,7 @@ def main():
         sync(device)
         t0 = time.perf_counter()
         for k in range(steps):
-            step(*(evs[k] if evs else ()))
+            last_res[0] = step(*(evs[k] if evs else ()))
         for k in range(2):
             w = pending[k]
             for ww in (w if isinstance(w, tuple) else (w,)):
@@ -868,18 +910,33 @@ def main():
         e1_.record()
     sync(device)
     elapsed = timed(args.steps, evs)
+    tot = None
     if exchange == "reduce" and not spot and args.steps:
         # fold the gathered slots of the last step: whole-job spot statistics
-        tot = hip.reduce_spot_slots(all_slots[(step_no[0] - 1) & 1].view(-1, 8)).cpu().numpy()
-        assert tot[0] > 0 or _DBG, "no ray reached the image plane"
+        tot = hip.reduce_spot_slots(all_slots[(step_no[0] - 1) & 1].view(-1, 8))
+        assert float(tot[0]) > 0 or _DBG, "no ray reached the image plane"
+    if args.dump_outputs and rank == 0 and args.steps:
+        # what a caller of the timed path receives from its last step (before any leg below
+        # reuses the record block)
+        res = last_res[0]
+        if opd_mode:
+            opd_, inten_, pupil_, mom_ = opd_out[0]
+            arrays = {"opd": opd_, "intensity": inten_, "pupil": pupil_, "moments": mom_}
+        elif spot:
+            arrays = {"moments": res}
+        else:
+            arrays = ({"record": res.record[:, :, :res.n]} if res.record is not None
+                      else {"rays": torch.stack(list(res.rays))})
+            if res.prt is not None:
+                arrays["prt"] = res.prt[:, :res.n]
+            if tot is not None:
+                arrays["spot_moments_job"] = tot
+            if exchange == "gather":  # (world, 3, n) image-plane hits of every rank
+                arrays["image_hits_job"] = gather_buf[(step_no[0] - 1) & 1][:, :, :n]
+        sync(device)
+        dump_outputs(args.dump_outputs, arrays, n)
     exchange_info = None
     if configured_exchange != "none" and args.steps:
-        # the same steps WITHOUT the image-plane exchange (outside the reported region):
-        # the difference is what the exchange costs per step, overlap included
-        exchange = "none"
-        step()  # untimed: the launch without the spot epilogue is a different kernel variant
-        bare = timed(args.steps)
-        exchange = configured_exchange
         wire = (8 * 64 * 8 if configured_exchange == "reduce" else 3 * b * n) if not spot \
             else (96 if opd_mode else 56)
         kinds = {"reduce": "async all-gather of the 4 KB spot-moment slot block (RCCL)",
@@ -887,10 +944,17 @@ def main():
         exchange_info = {
             "kind": kinds[configured_exchange] if not spot else "all-reduce of 7 doubles",
             "ms_per_step_with": elapsed / args.steps * 1e3,
-            "ms_per_step_without": bare / args.steps * 1e3,
-            "exchange_ms_per_step": (elapsed - bare) / args.steps * 1e3,
             "bytes_per_rank_per_step": wire,
         }
+    if exchange_info is not None and args.full:
+        # the same steps WITHOUT the image-plane exchange (outside the reported region):
+        # the difference is what the exchange costs per step, overlap included
+        exchange = "none"
+        step()  # untimed: the launch without the spot epilogue is a different kernel variant
+        bare = timed(args.steps)
+        exchange = configured_exchange
+        exchange_info["ms_per_step_without"] = bare / args.steps * 1e3
+        exchange_info["exchange_ms_per_step"] = (elapsed - bare) / args.steps * 1e3
         if not spot:
             # the OTHER exchange kind, same steps, outside the reported region
             other = "gather" if configured_exchange == "reduce" else "reduce"
@@ -918,15 +982,15 @@ def main():
     if have_pg:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
-    bw = device_bandwidth(device) if (rank == 0 and args.steps and not args.plumbing_check) \
-        else None
+    bw = device_bandwidth(device) if (args.full and rank == 0 and args.steps
+                                      and not args.plumbing_check) else None
     # Steady state, OUTSIDE the reported region: the same launch repeated until the part's
     # power management has settled (profiles/r04_clock_transient.txt: after ~1.5 ms of a
     # vector-ALU-heavy kernel the clocks drop by up to 40 % and take ~80 ms of sustained load
     # to come back -- exactly where a "5 warm-up + 20 timed" window sits; HBM-bound kernels
     # barely see it).  Mean of the last third of `--settle` more launches.
     steady = None
-    if rank == 0 and args.steps and args.settle > 0 and not args.plumbing_check:
+    if args.full and rank == 0 and args.steps and args.settle > 0 and not args.plumbing_check:
         sev = [(make_event(), make_event()) for _ in range(args.settle)]
         keep_exchange, exchange = exchange, "none"
         for e0_, e1_ in sev:
@@ -1029,7 +1093,8 @@ def main():
                 fill_big = stream_fill_bandwidth(hip, device, rb.numel(), b,
                                                  int(record.shape[0]) * 8, block=rb)
         live = None
-        if args.traffic == "live" and world == 1 and not args.plumbing_check and args.steps:
+        if args.full and args.traffic == "live" and world == 1 and not args.plumbing_check \
+                and args.steps:
             live = measure_traffic_live(
                 args, "opd_trace_kernel" if opd_mode else
                 ("spot_trace_kernel" if spot else "trace_kernel"))
@@ -1046,7 +1111,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
+            "ms_per_step": elapsed / args.steps * 1e3 if args.steps else None,
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
             "vs_baseline": None,
@@ -1143,7 +1208,7 @@ def main():
             },
         }
         gc.enable()  # (the GPU legs of this line are done)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             port = cpu_baseline(table, hy, "last" if spot else ("record" if gen else args.mode),
                                 args.cpu_seconds, wl)
             ref = None if args.no_ref_baselines else reference_baselines(

@@ -1,9 +1,9 @@
 """Locate / import the LIVE reference package for tests that need it.
 
-Build container: /root/reference.  GPU box: the copy staged by
-`oracle/stage_reference.py` under the git-ignored `oracle/_ref/` (test infrastructure,
-travels with the gpurun snapshot).  Import stubs for numba / vtk / seaborn, which the
-image lacks, are this repo's tests/refshim/.
+The package OPTILAND_REFERENCE points at, else the copy that `build()` stages with
+`oracle/stage_reference.py` under the git-ignored `oracle/_ref/` (test infrastructure).
+Import stubs for numba / vtk / seaborn, which the image lacks, are this repo's
+tests/refshim/.
 """
 
 from __future__ import annotations
@@ -14,11 +14,12 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SHIM = os.path.join(HERE, "refshim")
+STAGED = os.path.join(ROOT, "oracle", "_ref")
 
 
 def reference_root() -> str | None:
-    for cand in (os.environ.get("OPTILAND_REFERENCE"), "/root/reference",
-                 os.path.join(ROOT, "oracle", "_ref")):
+    """OPTILAND_REFERENCE if set, else the copy `build()` staged under oracle/_ref."""
+    for cand in (os.environ.get("OPTILAND_REFERENCE"), STAGED):
         if cand and os.path.isdir(os.path.join(cand, "optiland")):
             return cand
     return None

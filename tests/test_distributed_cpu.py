@@ -2,6 +2,7 @@
 
 import os
 import socket
+import traceback
 
 import numpy as np
 import pytest
@@ -191,9 +192,16 @@ def _field_worker(rank, world, port, q):
         assert out["result"].record.data_ptr() == block.data_ptr() == \
             first["result"].record.data_ptr()
         fresh = st.trace_field(0.0, 0.7, px, py, 0.5876, center=(0.0, 15.0))
-        assert torch.equal(fresh["result"].record.nan_to_num(), block.nan_to_num())
         res = out["result"]
+        # the launch writes the first res.n columns of every row; the columns past them are
+        # stride padding that no launch touches (whatever the allocator left there)
+        assert fresh["result"].n == res.n == out["hi"] - out["lo"]
+        assert torch.equal(fresh["result"].record[:, :, : res.n].nan_to_num(),
+                           block[:, :, : res.n].nan_to_num())
         q.put((rank, out["lo"], out["hi"], res.record[:, :, : res.n].numpy(), out["spot"]))
+    except BaseException:
+        q.put((rank, traceback.format_exc()))  # to the parent at once, not after its timeout
+        raise
     finally:
         dist.destroy_process_group()
 
@@ -217,6 +225,8 @@ def test_two_rank_one_launch_field_step_equals_single_process():
     for p in procs:
         p.start()
     results = sorted([q.get(timeout=150) for _ in range(world)], key=lambda t: t[0])
+    for res in results:
+        assert len(res) == 5, f"rank {res[0]} failed:\n{res[1]}"
     for p in procs:
         p.join(30)
         assert p.exitcode == 0

@@ -25,7 +25,9 @@ import sys
 import numpy as np
 import pytest
 
-REF = os.environ.get("OPTILAND_REFERENCE", "/root/reference")
+from tests import _live  # noqa: E402
+
+REF = _live.reference_root() or _live.STAGED  # the copy build() stages under oracle/_ref
 pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "optiland")),
                                 reason="reference package not present")
 

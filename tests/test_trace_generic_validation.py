@@ -17,7 +17,9 @@ import sys
 import numpy as np
 import pytest
 
-REF = os.environ.get("OPTILAND_REFERENCE", "/root/reference")
+from tests import _live  # noqa: E402
+
+REF = _live.reference_root() or _live.STAGED  # the copy build() stages under oracle/_ref
 needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "optiland")),
                                      reason="reference package not present")
 

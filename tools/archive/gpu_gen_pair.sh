@@ -10,7 +10,7 @@ echo "# bench.py --steps 20 --warmup 5 --no-cpu-baseline [--placement plain], OL
 for k in 1 2 3; do
  for rpt in 1 0; do
   for pl in probe plain; do
-   OL_TRACE_RPT=$rpt timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --placement $pl 2>/dev/null | tail -1 > /tmp/b.json
+   OL_TRACE_RPT=$rpt timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --placement $pl 2>/dev/null | tail -1 > /tmp/b.json
    python - "$rpt" "$pl" <<'PY' >> $out
 import json, sys
 d = json.load(open("/tmp/b.json")); r = d["roofline"]; p = r.get("record_placement") or {}; s = r.get("steady_state") or {}

@@ -7,7 +7,7 @@ out=gpurun_out/r04_pair_window.txt
 echo "# bench.py --mode record --steps 20 --warmup 5 --no-cpu-baseline, OL_TRACE_RPT = 1 | 3 (alternating, fresh processes)" > $out
 for k in 1 2 3; do
  for rpt in 1 3; do
-  OL_TRACE_RPT=$rpt timeout 300 python bench.py --mode record --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > /tmp/b.json
+  OL_TRACE_RPT=$rpt timeout 300 python bench.py --full --mode record --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > /tmp/b.json
   python - "$rpt" <<'PY' >> $out
 import json, sys
 d = json.load(open("/tmp/b.json")); r = d["roofline"]; p = r.get("record_placement") or {}; s = r.get("steady_state") or {}

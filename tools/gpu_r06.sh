@@ -83,7 +83,7 @@ PY
                  "c5_f32:--workload zernike_fresnel" "c5_f64:--workload zernike_fresnel --dtype f64" \
                  "dg_f64_spot:--mode spot --dtype f64" "dg_opd:--mode opd"; do
         tag=${cfg%%:*}; args=${cfg#*:}
-        python bench.py --steps 20 --warmup 5 --no-cpu-baseline --traffic committed $args \
+        python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --traffic committed $args \
           > $O/r06_bench_$tag.json 2> $O/r06_bench_$tag.err
         python - $O/r06_bench_$tag.json $tag <<'PY'
 import json, sys
@@ -101,7 +101,7 @@ PY
     exch)      # where the +0.05 ms per step of the reduce-first exchange go (one rank, RCCL)
       for dbg in none alwayswait nocoll; do
         OL_BENCH_EXCH_DEBUG=$dbg python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 \
-          bench.py --gpus 1 --force-exchange --steps 40 --warmup 10 --settle 0 --no-cpu-baseline --no-ref-baselines --traffic committed \
+          bench.py --full --gpus 1 --force-exchange --steps 40 --warmup 10 --settle 0 --no-cpu-baseline --no-ref-baselines --traffic committed \
           > $O/r06_exch_$dbg.json 2> $O/r06_exch_$dbg.err
         python - $O/r06_exch_$dbg.json $dbg <<'PY'
 import json, sys
@@ -114,7 +114,7 @@ PY
       done ;;
     bench1rank) # the N > 1 launch form with ONE rank: RCCL init, barrier, exchange legs, placement
       python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 \
-        bench.py --gpus 1 --force-exchange --steps 20 --warmup 5 --no-cpu-baseline --no-ref-baselines --traffic committed \
+        bench.py --full --gpus 1 --force-exchange --steps 20 --warmup 5 --no-cpu-baseline --no-ref-baselines --traffic committed \
         > $O/r06_bench_1rank_${TAG:-0}.json 2> $O/r06_bench_1rank_${TAG:-0}.err
       tail -c 1200 $O/r06_bench_1rank_${TAG:-0}.json; tail -3 $O/r06_bench_1rank_${TAG:-0}.err ;;
     c5_valu)   # SQ_INSTS_VALU per ray of the C5 launch against the Newton iteration cap (tools/gpu_c5_valu.py)
@@ -182,7 +182,7 @@ PY
       done; unset OPTILAND_HIP_LIBRARY ;;
     c5_window) # the driver's window (5 + 20 launches) of C5 fp32, one ray per lane against pairs, arms alternating
       for rep in 1 2 3; do for arm in 1 3; do
-        OL_TRACE_RPT=$arm python bench.py --steps 20 --warmup 5 --no-cpu-baseline --traffic committed --workload zernike_fresnel > $O/c5w_${arm}_${rep}.json 2>/dev/null
+        OL_TRACE_RPT=$arm python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --traffic committed --workload zernike_fresnel > $O/c5w_${arm}_${rep}.json 2>/dev/null
         python - $O/c5w_${arm}_${rep}.json $arm $rep <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
@@ -222,7 +222,7 @@ CFG
     fuzz_tables) # kernel vs oracle on every table under fuzz_tables/ (tools/make_fuzz_tables.py LO HI, CPU, beforehand)
       timeout 1500 python tools/gpu_fuzz_tables.py > $O/r06_fuzz_tables_${TAG:-0}.txt 2>&1; tail -15 $O/r06_fuzz_tables_${TAG:-0}.txt | cut -c1-250 ;;
     bench)
-      python bench.py ${BENCH_ARGS:-} > $O/r06_bench_${TAG:-default}.json 2> $O/r06_bench_${TAG:-default}.err
+      python bench.py --full ${BENCH_ARGS:-} > $O/r06_bench_${TAG:-default}.json 2> $O/r06_bench_${TAG:-default}.err
       tail -c 1500 $O/r06_bench_${TAG:-default}.json ;;
     *) echo "unknown leg $leg" ;;
   esac
