@@ -797,6 +797,28 @@ int ol_pupil_fill(ol_dtype dt, int64_t n_rays, const void* opd_waves, const void
                   const int32_t* cell, int32_t n_side, int32_t grid_size, double* grid,
                   void* stream);
 
+/* The Huygens-Fresnel summation of the Huygens PSF (optiland/psf/huygens_fresnel_strategies.py:
+ * 97-172 NumbaSummation, 184-274 TorchSummation; used by psf/huygens_fresnel.py:273-317 and
+ * psf/vectorial_huygens.py).  For image points P_m = (image[0..2])[m], m < n_image, and pupil
+ * samples Q_j = (pupil[0..2])[j], j < n_pupil, on the exit-pupil reference sphere of radius Rp:
+ *
+ *   field_m = sum_j a_j exp(i k (R_mj - opd_j)) / R_mj * 1/2 (1 + ((P_m - Q_j) . Q_j / Rp) / R_mj)
+ *   psf_m   = |field_m|^2,       k = 2 pi / wavelength_mm,   R_mj = |P_m - Q_j|
+ *
+ * (the Huygens-Fresnel principle with the Fresnel-Kirchhoff obliquity factor 1/2 (1 + cos theta):
+ * M. Born, E. Wolf, Principles of Optics, 7th ed., section 8.3).  pupil = {x, y, z, a, opd} in mm,
+ * the amplitude a real, or a + i amp_imag when amp_imag is given (vectorial PSF); all arrays are
+ * fp64 DEVICE arrays.  psf_out: n_image doubles; field_out (nullable): n_image interleaved
+ * (re, im) pairs.  fp64 throughout; the phase is carried in cycles and reduced exactly.  No
+ * sample is filtered: a NaN sample makes every pixel NaN, as in the reference.  The sums are
+ * formed in a fixed order that depends on (n_pupil, n_image) only: bit-identical from run to
+ * run.  Stream-ordered workspace (hipMallocAsync, 64 B per pupil sample + 16 B per pixel and
+ * pupil chunk).  OL_EINVAL: NULL arrays, a negative count, wavelength_mm <= 0, Rp = 0 or NaN.
+ * n_image = 0 is a no-op; n_pupil = 0 writes zeros.                                        */
+int ol_huygens_psf(int64_t n_pupil, const double* const pupil[5], const double* amp_imag,
+                   int64_t n_image, const double* const image[3], double wavelength_mm,
+                   double Rp, double* psf_out, double* field_out, void* stream);
+
 /* Profiling knobs (process-wide, not part of the trace semantics).
  *   OL_TUNE_RAYS_PER_THREAD  0 = auto (16-byte vector of rays per lane for conic-only
  *                            ranges, one ray per lane when Newton surfaces are

@@ -144,6 +144,7 @@ EXPORTS = (
     "ol_newton_count",
     "ol_arena_alloc",
     "ol_arena_free",
+    "ol_huygens_psf",
 )
 
 F32, F64 = 0, 1
@@ -273,7 +274,18 @@ def bind(lib, path: str = "?"):
     lib.ol_math_probe.argtypes = [i32, C.c_int, i64, vp, vp, vp, vp]
     lib.ol_stream_fill.restype = C.c_int
     lib.ol_stream_fill.argtypes = [vp, i64, i32, i32, u32, vp]
+    # (additive within ABI 11: bound only where the library has it -- the host-math harness
+    # and older builds do not; `huygens_sum` then asks for a rebuild when it is used)
+    if hasattr(lib, "ol_huygens_psf"):
+        lib.ol_huygens_psf.restype = C.c_int
+        lib.ol_huygens_psf.argtypes = [i64, C.POINTER(vp), vp, i64, C.POINTER(vp), C.c_double,
+                                       C.c_double, vp, vp, vp]
     return lib
+
+
+def has_huygens(lib) -> bool:
+    """True when the loaded library exports ol_huygens_psf."""
+    return hasattr(lib, "ol_huygens_psf")
 
 
 def check(rc: int, what: str, lib=None) -> None:

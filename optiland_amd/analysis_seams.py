@@ -51,7 +51,7 @@ _ORIG: dict = {}
 STATS = {"spot": 0, "spot_fallback": 0, "ee": 0, "ee_fallback": 0, "opd": 0, "opd_fallback": 0,
          "pupil": 0, "pupil_fallback": 0, "opd_init": 0, "opd_init_fallback": 0,
          "dist": 0, "dist_fallback": 0, "opd_fit": 0, "opd_fit_fallback": 0, "spot_grid": 0,
-         "spot_radius": 0}
+         "spot_radius": 0, "huygens": 0, "huygens_fallback": 0}
 
 
 def _why(seam, reason):
@@ -1153,6 +1153,68 @@ def _uniform_generate_points(self, num_points):
     return None
 
 
+# --------------------------------------------------------------------------- Huygens PSF
+_HUYGENS_ARGS = ("image_x", "image_y", "image_z", "pupil_x", "pupil_y", "pupil_z", "pupil_amp",
+                 "pupil_opd", "wavelength", "Rp")
+
+
+def _huygens_torch_compute(self, image_x, image_y, image_z, pupil_x, pupil_y, pupil_z,
+                           pupil_amp, pupil_opd, wavelength, Rp):
+    """psf/huygens_fresnel_strategies.py:184-274 (`TorchSummation.compute`) with
+    `ol_huygens_psf`: the O(pixels x rays) sum in one fp64 kernel instead of complex
+    temporaries of 1024 pixels x all rays per batch.  `HuygensPSF`, `VectorialHuygensPSF`
+    (complex amplitudes) and `HuygensMTF` call it.  Same shape and dtype as the reference (a
+    float32 backend gets the fp64 sum cast down: closer to the exact sum than the reference's
+    own float32 one).  Falls back to the reference's method off the HIP device, under
+    autograd, or with a library that lacks the kernel."""
+    args = (image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, pupil_amp, pupil_opd,
+            wavelength, Rp)
+    out = _huygens_device(self, *args)
+    if out is None:
+        STATS["huygens_fallback"] += 1
+        return _ORIG["huygens"](self, *args)
+    STATS["huygens"] += 1
+    return out
+
+
+def _huygens_device(self, *args):
+    import optiland.backend as be
+
+    from . import _capi
+
+    dev = torch.device(getattr(self, "device", None) or "cpu")
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        _why("huygens", f"summation device {dev} is not a HIP device")
+        return None
+    tensors = [a for a in args if isinstance(a, torch.Tensor)]
+    try:
+        grad = be._backends[be.get_backend()]._config.grad_mode.requires_grad
+    except Exception:  # noqa: BLE001 - a backend without that configuration object
+        grad = False
+    if grad or any(t.requires_grad for t in tensors):
+        _why("huygens", "autograd")
+        return None
+    if any(t.device.type != "cuda" for t in tensors):
+        _why("huygens", "an input lives off the HIP device")
+        return None
+    try:
+        lib = _capi.load()
+    except _capi.HipExtensionError as exc:
+        _why("huygens", str(exc))
+        return None
+    if not _capi.has_huygens(lib):
+        _why("huygens", "library without ol_huygens_psf")
+        return None
+    from .engine import huygens_sum
+
+    image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd, wavelength, Rp = \
+        [a.detach() if isinstance(a, torch.Tensor) else a for a in args]
+    psf = huygens_sum(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd,
+                      _f(wavelength), _f(Rp), device=dev)
+    real = torch.float32 if be.get_complex_precision() == torch.complex64 else torch.float64
+    return psf.to(real)
+
+
 # --------------------------------------------------------------------------- (de)activate
 # The seams replace PRIVATE methods of the reference.  Each entry: key in _ORIG -> (module,
 # class, method, the parameter names the replacement was written against, replacement).  A
@@ -1197,6 +1259,8 @@ _SEAMS = {
     "fft_init": ("optiland.psf.fft", "ScalarFFTPSF", "__init__",
                  ("self", "optic", "field", "wavelength", "num_rays", "grid_size", "strategy",
                   "remove_tilt", "kwargs"), "_fft_init"),
+    "huygens": ("optiland.psf.huygens_fresnel_strategies", "TorchSummation", "compute",
+                ("self",) + _HUYGENS_ARGS, "_huygens_torch_compute"),
 }
 def _constructor_scope(key):
     """A constructor of the reference that only READS its optic -- `Wavefront.__init__`

@@ -19,6 +19,7 @@
 
 #include "../../include/optiland_hip.h"
 #include "device_table.h"
+#include "last_error.h"
 #include "trace_launch.h"
 
 namespace {
@@ -736,6 +737,8 @@ int do_trace_opd(const ol_system* sys, const DeviceTable<T>& tab, int64_t n,
 }
 
 }  // namespace
+
+int ol::set_last_error(int code, const char* message) { return fail(code, "%s", message); }
 
 extern "C" {
 

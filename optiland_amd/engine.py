@@ -1573,3 +1573,60 @@ class HipSystem:
                                          float(cy), out.data_ptr(), self._stream())
         self._check(rc, "ol_spot_max_r2")
         return out
+
+    def huygens_sum(self, *args, **kwargs):
+        """`huygens_sum` (module level) on this system's device."""
+        return huygens_sum(*args, device=self.device, **kwargs)
+
+
+def huygens_sum(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd_mm,
+                wavelength_mm: float, Rp: float, *, want_field: bool = False, device=None):
+    """`ol_huygens_psf`: the Huygens-Fresnel sum of psf/huygens_fresnel_strategies.py:97-172 on
+    the device, fp64 throughout (fp32 inputs are widened).
+
+    image_*: the image points (any shape, one shape for the three); pupil_* / amp / opd_mm:
+    the pupil samples (flattened), `amp` real or complex (the vectorial PSF's amplitudes).
+    Returns psf = |field|^2 (float64, image_x's shape) or, with `want_field`, (psf, field)
+    with field complex128.  Tensors on another device are copied to `device` (default: the
+    current HIP device); host arrays are accepted too."""
+    lib = _capi.load()
+    if not _capi.has_huygens(lib):
+        raise _capi.HipExtensionError(
+            f"{_capi.library_path()} has no ol_huygens_psf; rebuild the library "
+            "(`python -c 'import __graft_entry__ as g; g.build()'`)")
+    dev = _require_gpu(device)
+
+    def plane(v):
+        t = torch.as_tensor(v, device=dev)
+        if t.is_complex():
+            raise ValueError("huygens_sum: only the amplitude may be complex")
+        return t.to(torch.float64).reshape(-1).contiguous()
+
+    shape = tuple(torch.as_tensor(image_x).shape)
+    img = [plane(v) for v in (image_x, image_y, image_z)]
+    m = img[0].numel()
+    if any(t.numel() != m for t in img):
+        raise ValueError("huygens_sum: image_x / image_y / image_z differ in size")
+    a = torch.as_tensor(amp, device=dev)
+    a_im = None
+    if a.is_complex():
+        a = a.to(torch.complex128).reshape(-1)
+        a, a_im = a.real.contiguous(), a.imag.contiguous()
+    else:
+        a = plane(a)
+    pup = [plane(v) for v in (pupil_x, pupil_y, pupil_z)] + [a, plane(opd_mm)]
+    n = pup[0].numel()
+    if any(t.numel() != n for t in pup) or (a_im is not None and a_im.numel() != n):
+        raise ValueError("huygens_sum: the pupil arrays differ in size")
+    psf = torch.empty(m, dtype=torch.float64, device=dev)
+    field = torch.empty(m, dtype=torch.complex128, device=dev) if want_field else None
+    pp = (C.c_void_p * 5)(*[t.data_ptr() for t in pup])
+    ip = (C.c_void_p * 3)(*[t.data_ptr() for t in img])
+    with torch.cuda.device(dev):
+        rc = lib.ol_huygens_psf(n, pp, a_im.data_ptr() if a_im is not None else None, m, ip,
+                                float(wavelength_mm), float(Rp), psf.data_ptr(),
+                                field.data_ptr() if field is not None else None,
+                                _stream_ptr(dev))
+    _capi.check(rc, "ol_huygens_psf", lib)
+    psf = psf.reshape(shape)
+    return (psf, field.reshape(shape)) if want_field else psf

@@ -359,3 +359,131 @@ class FFTPSF:
         """psf/base.py:418-438."""
         c = self.psf.shape[0] // 2
         return float(self.psf[c, self.psf.shape[1] // 2]) / 100
+
+
+class HuygensPSF:
+    """Scalar Huygens-Fresnel PSF (psf/huygens_fresnel.py:31-348 `ScalarHuygensPSF`) for one
+    field and wavelength: the pupil samples of the device wavefront (uniform grid, fp64)
+    summed onto a grid of image points by `ol_huygens_psf`, normalised to 100 at the peak of
+    the ideal (zero-OPD, unit-amplitude) pupil.  Planar, unrotated image surfaces only: the
+    drop-in (analysis_seams) takes its image points from the reference and covers the rest."""
+
+    MAX_FNUM = 10000.0  # utils.py:68
+
+    def __init__(self, tracer, field, wavelength, num_rays: int = 128, image_size: int = 128,
+                 strategy: str = "chief_ray", remove_tilt: bool = False, oversample=None,
+                 pixel_pitch=None, normalization=None):
+        self.tracer = tracer
+        self.field = (float(field[0]), float(field[1]))
+        self.wavelength = float(wavelength)
+        self.num_rays, self.image_size = int(num_rays), int(image_size)
+        self.oversample = oversample
+        self.pixel_pitch = None if pixel_pitch is None else float(pixel_pitch)
+        self.normalization = None if normalization is None else float(normalization)
+        self.cx = self.cy = None
+        self._image_origin = self._planar_image_surface()
+        self.wavefront = Wavefront(tracer, self.field, self.wavelength, self.num_rays, "uniform",
+                                   strategy=strategy, remove_tilt=remove_tilt)
+        self.psf = self._compute_psf()
+
+    def _planar_image_surface(self):
+        from . import system as S
+        s = self.tracer.table.surfaces[-1]
+        plane = int(s["geom_kind"]) == S.GEOM_PLANE or (
+            int(s["geom_kind"]) == S.GEOM_STANDARD and not math.isfinite(float(s["radius"])))
+        if not plane or int(s["flags"]) & S.SURF_ROTATED:
+            raise ValueError("HuygensPSF: the stand-alone class needs a planar, unrotated image "
+                             "surface (use the reference's HuygensPSF through the drop-in)")
+        return [float(v) for v in s["origin"]]
+
+    def _sum(self, image, pupil, amp, opd_mm, Rp, device):
+        from .engine import huygens_sum
+        return huygens_sum(*image, *pupil, amp, opd_mm, self.wavelength * 1e-3, Rp,
+                           device=device)
+
+    def _determine_image_center(self):
+        """huygens_fresnel.py:119-144: 6 hexapolar rings, rays with i > 0, image-local x / y."""
+        rays = self.tracer.trace(self.field[0], self.field[1], self.wavelength, 6, "hexapolar")
+        ok = rays.i > 0
+        if not bool(ok.any()):
+            return np.array([0.0]), np.array([0.0])
+        ox, oy, _ = self._image_origin
+        return ((rays.x[ok].double() - ox).cpu().numpy(),
+                (rays.y[ok].double() - oy).cpu().numpy())
+
+    def working_fno(self) -> float:
+        """utils.py:45-106 get_working_FNO: chief ray + four marginal rays."""
+        t = self.tracer
+        wl, _ = t._wavelength_index(self.wavelength)
+        n = float(t.table.optics[-1, wl]["n2"])
+        px = np.array([0.0, 0.0, 0.0, 1.0, -1.0])
+        py = np.array([0.0, 1.0, -1.0, 0.0, 0.0])
+        r = t.trace_generic(self.field[0], self.field[1], px, py, self.wavelength)
+        L, M, N, i = (torch.as_tensor(v).double().reshape(-1).cpu().numpy()
+                      for v in (r.L, r.M, r.N, r.i))
+        dot = np.clip(L[0] * L[1:] + M[0] * M[1:] + N[0] * N[1:], -1.0, 1.0)
+        na2 = (n * np.sin(np.arccos(dot))) ** 2
+        valid = i[1:] > 0
+        avg = float(np.mean(na2[valid] if valid.any() else na2))
+        fno = math.inf if avg <= 0 else 1 / (2 * math.sqrt(avg))
+        fno = min(fno, self.MAX_FNUM)
+        if math.isnan(fno):
+            raise ValueError("Working F/# could not be calculated due to raytrace errors.")
+        return fno
+
+    def _get_image_extent(self):
+        """huygens_fresnel.py:146-210."""
+        rx, ry = self._determine_image_center()
+        self.cx, self.cy = float(np.mean(rx)), float(np.mean(ry))
+        wl_mm = self.wavelength * 1e-3
+        if self.pixel_pitch is not None:
+            extent = 0.5 * self.image_size * self.pixel_pitch
+        else:
+            if self.oversample is not None:
+                f_cutoff = 1.0 / (self.working_fno() * wl_mm)
+                self.pixel_pitch = 1.0 / (2 * self.oversample * f_cutoff)
+                extent = 0.5 * self.image_size * self.pixel_pitch
+            else:
+                geometric = float(np.max(np.hypot(rx - self.cx, ry - self.cy)))
+                ideal = 5.0 * self.working_fno() * 1.22 * wl_mm
+                extent = max(geometric, ideal)
+            self.pixel_pitch = 2 * extent / self.image_size
+        return -extent + self.cx, extent + self.cx, -extent + self.cy, extent + self.cy
+
+    def _get_image_coordinates(self, device):
+        """huygens_fresnel.py:212-237 on a planar image surface (sag 0), local -> global."""
+        xmin, xmax, ymin, ymax = self._get_image_extent()
+        kw = dict(dtype=torch.float64, device=device)
+        gx, gy = torch.meshgrid(torch.linspace(xmin, xmax, self.image_size, **kw),
+                                torch.linspace(ymin, ymax, self.image_size, **kw), indexing="xy")
+        ox, oy, oz = self._image_origin
+        return gx + ox, gy + oy, torch.full_like(gx, oz)
+
+    def _get_normalization(self, data, device) -> float:
+        """huygens_fresnel.py:239-286: the ideal pupil's PSF at the on-axis image point."""
+        if self.field != (0.0, 0.0):
+            data = Wavefront(self.tracer, (0.0, 0.0), self.wavelength, self.num_rays,
+                             "uniform").data
+        kw = dict(dtype=torch.float64, device=device)
+        point = [torch.zeros((1, 1), **kw), torch.zeros((1, 1), **kw),
+                 torch.full((1, 1), self._image_origin[2], **kw)]
+        psf = self._sum(point, (data.pupil_x, data.pupil_y, data.pupil_z),
+                        torch.ones_like(data.intensity), torch.zeros_like(data.opd),
+                        float(data.radius), device)
+        return float(psf[0, 0])
+
+    def _compute_psf(self) -> torch.Tensor:
+        """huygens_fresnel.py:288-324."""
+        d = self.wavefront.data
+        device = d.opd.device
+        wl_mm = self.wavelength * 1e-3
+        image = self._get_image_coordinates(device)
+        psf = self._sum(image, (d.pupil_x, d.pupil_y, d.pupil_z), torch.sqrt(d.intensity),
+                        d.opd * wl_mm, float(d.radius), device)
+        if self.normalization is None:
+            self.normalization = self._get_normalization(d, device)
+        return psf / self.normalization * 100.0
+
+    def strehl_ratio(self) -> float:
+        """psf/base.py:418-438."""
+        return float(self.psf[self.psf.shape[0] // 2, self.psf.shape[1] // 2]) / 100
