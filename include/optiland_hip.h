@@ -819,6 +819,42 @@ int ol_huygens_psf(int64_t n_pupil, const double* const pupil[5], const double* 
                    int64_t n_image, const double* const image[3], double wavelength_mm,
                    double Rp, double* psf_out, double* field_out, void* stream);
 
+/* The geometric MTF of image-plane hits (optiland/mtf/geometric.py:152-204 `GeometricMTF.
+ * _generate_mtf_data` / `_compute_field_data`, on the reference's NumPy backend; W. J. Smith,
+ * Modern Optical Engineering, 3rd ed., section 11.9).  For each of the n_curves coordinate arrays
+ * (coords[c]: lengths[c] values of type `dt` on the DEVICE; coords and lengths themselves are
+ * HOST arrays) -- the x or the y of one field's hits --
+ *
+ *   A, edges = np.histogram(coords[c], bins = n_bins)      x_j = (edges[j + 1] + edges[j]) / 2
+ *   mtf[c][k] = scale[k] * hypot(sum_j A_j cos(2 pi freq[k] x_j),
+ *                                sum_j A_j sin(2 pi freq[k] x_j)) / sum_j A_j
+ *
+ * freq (cycles / mm) and scale (nullable: 1) are fp64 device arrays of num_points entries.
+ * Outputs, all on the device: mtf_out n_curves x num_points doubles; counts_out (nullable)
+ * n_curves x n_bins int32, EQUAL to np.histogram's counts of the widened values (range = min
+ * and max of the curve, min - 0.5 / max + 0.5 when they coincide; edges = np.linspace(min, max,
+ * n_bins + 1) with its separately rounded product and sum; bins closed on the left, the last
+ * one on both sides); edges_minmax_out n_curves x 2 doubles, the first and the last edge;
+ * flags_out n_curves int32: OL_MTF_NONFINITE when the curve holds a NaN or an infinity
+ * (np.histogram raises ValueError for it) -- that curve's mtf and edges are NaN, its counts 0,
+ * and the other curves are unaffected.  A curve without points: edges (0, 1), counts 0, mtf
+ * NaN (0 / 0, as in the reference).
+ * fp64 throughout (OL_F32 coordinates are widened on load); the phase freq x is carried in
+ * cycles, measured from the curve's minimum (the modulus does not see the shift) and reduced
+ * exactly.  Three launches on `stream` whatever n_curves is; integer atomics only and a fixed
+ * summation order over the bins: bit-identical from run to run, and a curve's result does not
+ * depend on the other curves of the call.  Stream-ordered workspace (hipMallocAsync).
+ * OL_EINVAL: a dtype other than OL_F32 / OL_F64, n_curves outside 0..OL_MTF_MAX_CURVES, n_bins
+ * outside 1..OL_MTF_MAX_BINS, a negative count or one above INT32_MAX, NULL arrays.
+ * n_curves = 0 is a no-op.                                                                  */
+#define OL_MTF_MAX_CURVES 64
+#define OL_MTF_MAX_BINS 8192
+#define OL_MTF_NONFINITE 1
+int ol_geometric_mtf(ol_dtype dt, int32_t n_curves, const void* const* coords,
+                     const int64_t* lengths, int32_t num_points, const double* freq,
+                     const double* scale, int32_t n_bins, double* mtf_out, int32_t* counts_out,
+                     double* edges_minmax_out, int32_t* flags_out, void* stream);
+
 /* Profiling knobs (process-wide, not part of the trace semantics).
  *   OL_TUNE_RAYS_PER_THREAD  0 = auto (16-byte vector of rays per lane for conic-only
  *                            ranges, one ray per lane when Newton surfaces are

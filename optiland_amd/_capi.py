@@ -145,6 +145,7 @@ EXPORTS = (
     "ol_arena_alloc",
     "ol_arena_free",
     "ol_huygens_psf",
+    "ol_geometric_mtf",
 )
 
 F32, F64 = 0, 1
@@ -280,7 +281,19 @@ def bind(lib, path: str = "?"):
         lib.ol_huygens_psf.restype = C.c_int
         lib.ol_huygens_psf.argtypes = [i64, C.POINTER(vp), vp, i64, C.POINTER(vp), C.c_double,
                                        C.c_double, vp, vp, vp]
+    if hasattr(lib, "ol_geometric_mtf"):   # (additive within ABI 11, like ol_huygens_psf)
+        lib.ol_geometric_mtf.restype = C.c_int
+        lib.ol_geometric_mtf.argtypes = [C.c_int, i32, C.POINTER(vp), C.POINTER(i64), i32, vp, vp,
+                                         i32, vp, vp, vp, vp, vp]
     return lib
+
+
+MTF_MAX_CURVES, MTF_MAX_BINS, MTF_NONFINITE = 64, 8192, 1   # OL_MTF_* (optiland_hip.h)
+
+
+def has_geometric_mtf(lib) -> bool:
+    """True when the loaded library exports ol_geometric_mtf."""
+    return hasattr(lib, "ol_geometric_mtf")
 
 
 def has_huygens(lib) -> bool:

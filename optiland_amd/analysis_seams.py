@@ -23,7 +23,9 @@ for exactly that:
   decisions between them as a chain of device passes with one read-back at the end;
 * `HexagonalDistribution.generate_points` (distribution.py:201-220) -> `ol_pupil_points`: the
   pupil grid of an analysis in one launch instead of a Python loop over the rings (round 4:
-  10 of the 11 ms of an OPD at 256 rings).
+  10 of the 11 ms of an OPD at 256 rings);
+* `GeometricMTF._generate_mtf_data` (mtf/geometric.py:152-177) -> `ol_geometric_mtf`: histogram
+  and transform of every field's two curves in three kernels.
 
 Every patched method first asks whether the call is one the fused path covers -- drop-in
 active for this optic, torch backend on the HIP device without autograd, a system the
@@ -51,7 +53,8 @@ _ORIG: dict = {}
 STATS = {"spot": 0, "spot_fallback": 0, "ee": 0, "ee_fallback": 0, "opd": 0, "opd_fallback": 0,
          "pupil": 0, "pupil_fallback": 0, "opd_init": 0, "opd_init_fallback": 0,
          "dist": 0, "dist_fallback": 0, "opd_fit": 0, "opd_fit_fallback": 0, "spot_grid": 0,
-         "spot_radius": 0, "huygens": 0, "huygens_fallback": 0}
+         "spot_radius": 0, "huygens": 0, "huygens_fallback": 0, "geo_mtf": 0,
+         "geo_mtf_fallback": 0}
 
 
 def _why(seam, reason):
@@ -1215,6 +1218,82 @@ def _huygens_device(self, *args):
     return psf.to(real)
 
 
+# --------------------------------------------------------------------------- geometric MTF
+def _geometric_mtf_generate(self):
+    """mtf/geometric.py:152-177 (`GeometricMTF._generate_mtf_data`) with `ol_geometric_mtf`: the
+    histogram and the transform of every field's two curves in ONE call (three kernels) instead
+    of 2 F `be.histogram` calls and a Python loop over the frequencies.  `self.data` are the
+    spot seam's device tensors.  Same shapes as the reference, in the backend's precision; the
+    NUMBERS are those of the reference's NumPy backend (an fp64 `np.histogram`), not of its
+    torch backend, whose `torch.histogram(x.float())` bins in float32.  Falls back to the
+    reference's method off the HIP device, under autograd, with a library that lacks the kernel,
+    and for a non-finite hit (the user then sees the reference's own error)."""
+    out = _geometric_mtf_device(self)
+    if out is None:
+        STATS["geo_mtf_fallback"] += 1
+        return _ORIG["geo_mtf"](self)
+    STATS["geo_mtf"] += 1
+    return out
+
+
+def _geometric_mtf_device(self):
+    import optiland.backend as be
+
+    from . import _capi
+
+    if be.get_backend() != "torch" or not torch.cuda.is_available():
+        _why("geo_mtf", "not the torch backend on a HIP device")
+        return None
+    try:
+        curves = [c for field_data in self.data for c in (field_data[0].y, field_data[0].x)]
+    except (AttributeError, IndexError, TypeError):
+        _why("geo_mtf", "self.data is not a grid of SpotData")
+        return None
+    freq = self.freq
+    tensors = curves + [freq]
+    if not curves or any(not isinstance(t, torch.Tensor) or t.device.type != "cuda"
+                         or not t.is_floating_point() or t.ndim != 1 for t in tensors):
+        _why("geo_mtf", "hits or frequencies live off the HIP device")
+        return None
+    try:
+        grad = be._backends[be.get_backend()]._config.grad_mode.requires_grad
+    except Exception:  # noqa: BLE001 - a backend without that configuration object
+        grad = False
+    if grad or any(t.requires_grad for t in tensors):
+        _why("geo_mtf", "autograd")
+        return None
+    n_bins = int(self.num_points) + 1
+    if not 1 <= n_bins <= _capi.MTF_MAX_BINS or freq.numel() < 1:
+        _why("geo_mtf", f"{n_bins} bins")
+        return None
+    try:
+        lib = _capi.load()
+    except _capi.HipExtensionError as exc:
+        _why("geo_mtf", str(exc))
+        return None
+    if not _capi.has_geometric_mtf(lib):
+        _why("geo_mtf", "library without ol_geometric_mtf")
+        return None
+    from .engine import geometric_mtf_launch
+
+    real = freq.dtype
+    if self.scale:   # geometric.py:160-163, on the device in fp64
+        f64 = freq.detach().to(torch.float64)
+        phi = torch.arccos(torch.clip(f64 / _f(self.cutoff_freq), 0.0, 1.0))
+        scale64 = 2 / math.pi * (phi - torch.cos(phi) * torch.sin(phi))
+        scale_factor = scale64.to(real)
+    else:
+        scale64, scale_factor = None, 1
+    mtf, _counts, _edges, flags = geometric_mtf_launch(
+        [c.detach() for c in curves], freq.detach(), scale64, n_bins, device=freq.device)
+    # the ONE read-back: the flag words
+    if bool(flags.any()):
+        _why("geo_mtf", "a non-finite hit")
+        return None
+    mtf = mtf.to(real)
+    return [[mtf[2 * k], mtf[2 * k + 1]] for k in range(len(self.data))], scale_factor
+
+
 # --------------------------------------------------------------------------- (de)activate
 # The seams replace PRIVATE methods of the reference.  Each entry: key in _ORIG -> (module,
 # class, method, the parameter names the replacement was written against, replacement).  A
@@ -1261,6 +1340,8 @@ _SEAMS = {
                   "remove_tilt", "kwargs"), "_fft_init"),
     "huygens": ("optiland.psf.huygens_fresnel_strategies", "TorchSummation", "compute",
                 ("self",) + _HUYGENS_ARGS, "_huygens_torch_compute"),
+    "geo_mtf": ("optiland.mtf.geometric", "GeometricMTF", "_generate_mtf_data", ("self",),
+                "_geometric_mtf_generate"),
 }
 def _constructor_scope(key):
     """A constructor of the reference that only READS its optic -- `Wavefront.__init__`

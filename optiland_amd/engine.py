@@ -1630,3 +1630,97 @@ def huygens_sum(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd_m
     _capi.check(rc, "ol_huygens_psf", lib)
     psf = psf.reshape(shape)
     return (psf, field.reshape(shape)) if want_field else psf
+
+
+def _mtf_arguments(coords, freq, scale, n_bins):
+    """The host-side checks of `geometric_mtf` (nothing here touches a device): the curves as a
+    list of 1-D arrays / tensors, (num_points, n_bins)."""
+    if isinstance(coords, (torch.Tensor, np.ndarray)):
+        if coords.ndim not in (1, 2):
+            raise ValueError("geometric_mtf: coords must be a sequence of 1-D arrays or a "
+                             f"(curves, points) array, got {coords.ndim} dimensions")
+        coords = [coords] if coords.ndim == 1 else list(coords)
+    coords = list(coords)
+    if not coords:
+        raise ValueError("geometric_mtf: no curve given")
+    for k, c in enumerate(coords):
+        shape = tuple(getattr(c, "shape", np.shape(c)))
+        if len(shape) != 1:
+            raise ValueError(f"geometric_mtf: coords[{k}] must be one-dimensional, got {shape}")
+        if isinstance(c, torch.Tensor) and (c.is_complex() or not c.is_floating_point()):
+            raise ValueError(f"geometric_mtf: coords[{k}] must be real floating point, "
+                             f"got {c.dtype}")
+    fshape = tuple(getattr(freq, "shape", np.shape(freq)))
+    if len(fshape) != 1 or fshape[0] < 1:
+        raise ValueError(f"geometric_mtf: freq must be a non-empty 1-D array, got shape {fshape}")
+    num_points = int(fshape[0])
+    if scale is not None:
+        sshape = tuple(getattr(scale, "shape", np.shape(scale)))
+        if sshape != (num_points,):
+            raise ValueError(f"geometric_mtf: scale has shape {sshape}, freq {fshape}")
+    if n_bins is None:
+        n_bins = num_points + 1      # geometric.py:193
+    if isinstance(n_bins, bool) or int(n_bins) != n_bins:
+        raise ValueError(f"geometric_mtf: n_bins must be an integer, got {n_bins!r}")
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= _capi.MTF_MAX_BINS:
+        raise ValueError(f"geometric_mtf: n_bins {n_bins} is outside 1..{_capi.MTF_MAX_BINS}")
+    return coords, num_points, n_bins
+
+
+def geometric_mtf_launch(coords, freq, scale=None, n_bins=None, *, device=None):
+    """`ol_geometric_mtf` without the read-back: (mtf (curves, num_points) float64, counts
+    (curves, n_bins) int32, edges_minmax (curves, 2) float64, flags (curves,) int32), all device
+    tensors; a curve whose flag is `_capi.MTF_NONFINITE` holds NaN.  Float32 curves are handed
+    over as they are (widened on load) when every curve is float32, anything else as float64.
+    More than `_capi.MTF_MAX_CURVES` curves go out as several calls."""
+    coords, num_points, n_bins = _mtf_arguments(coords, freq, scale, n_bins)
+    lib = _capi.load()
+    if not _capi.has_geometric_mtf(lib):
+        raise _capi.HipExtensionError(
+            f"{_capi.library_path()} has no ol_geometric_mtf; rebuild the library "
+            "(`python -c 'import __graft_entry__ as g; g.build()'`)")
+    dev = _require_gpu(device)
+    all_f32 = all(isinstance(c, torch.Tensor) and c.dtype == torch.float32 for c in coords)
+    dtype = torch.float32 if all_f32 else torch.float64
+    planes = [torch.as_tensor(c, device=dev).detach().to(dtype).contiguous() for c in coords]
+    v = torch.as_tensor(freq, device=dev).detach().to(torch.float64).contiguous()
+    s = None if scale is None else \
+        torch.as_tensor(scale, device=dev).detach().to(torch.float64).contiguous()
+    k = len(planes)
+    mtf = torch.empty((k, num_points), dtype=torch.float64, device=dev)
+    counts = torch.empty((k, n_bins), dtype=torch.int32, device=dev)
+    edges = torch.empty((k, 2), dtype=torch.float64, device=dev)
+    flags = torch.empty(k, dtype=torch.int32, device=dev)
+    step = _capi.MTF_MAX_CURVES
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        for lo in range(0, k, step):
+            part = planes[lo:lo + step]
+            ptrs = (C.c_void_p * len(part))(*[p.data_ptr() if p.numel() else None for p in part])
+            lens = (C.c_int64 * len(part))(*[p.numel() for p in part])
+            rc = lib.ol_geometric_mtf(_DT[dtype], len(part), ptrs, lens, num_points,
+                                      v.data_ptr(), s.data_ptr() if s is not None else None,
+                                      n_bins, mtf[lo].data_ptr(), counts[lo].data_ptr(),
+                                      edges[lo].data_ptr(), flags[lo:].data_ptr(), stream)
+            _capi.check(rc, "ol_geometric_mtf", lib)
+    return mtf, counts, edges, flags
+
+
+def geometric_mtf(coords, freq, scale=None, n_bins=None, want_counts=False, *, device=None):
+    """The geometric MTF of mtf/geometric.py:179-204 (`GeometricMTF._compute_field_data`, the
+    NumPy backend's fp64 numbers) for several curves in one `ol_geometric_mtf` call.
+
+    coords: a sequence of 1-D coordinate arrays (the x or the y of a field's hits, in mm; their
+    lengths may differ) or one (curves, points) array; freq: (num_points,) cycles / mm; scale:
+    optional (num_points,) factor per frequency; n_bins: default num_points + 1, as in the
+    reference.  Returns mtf, a (curves, num_points) float64 device tensor, or with `want_counts`
+    (mtf, counts, edges_minmax): np.histogram's counts (int32) and its first / last edge per
+    curve.  Raises the ValueError np.histogram raises when a curve holds a NaN or an infinity
+    (one read-back of the flag words)."""
+    mtf, counts, edges, flags = geometric_mtf_launch(coords, freq, scale, n_bins, device=device)
+    bad = torch.nonzero(flags).reshape(-1).tolist()
+    if bad:
+        raise ValueError(f"autodetected range of curve {bad[0]} is not finite "
+                         "(a NaN or an infinite coordinate)")
+    return (mtf, counts, edges) if want_counts else mtf

@@ -361,6 +361,29 @@ class FFTPSF:
         return float(self.psf[c, self.psf.shape[1] // 2]) / 100
 
 
+MAX_FNUM = 10000.0  # utils.py:68
+
+
+def working_fno(t, field, wavelength) -> float:
+    """utils.py:45-106 get_working_FNO: chief ray + four marginal rays."""
+    wl, _ = t._wavelength_index(wavelength)
+    n = float(t.table.optics[-1, wl]["n2"])
+    px = np.array([0.0, 0.0, 0.0, 1.0, -1.0])
+    py = np.array([0.0, 1.0, -1.0, 0.0, 0.0])
+    r = t.trace_generic(field[0], field[1], px, py, wavelength)
+    L, M, N, i = (torch.as_tensor(v).double().reshape(-1).cpu().numpy()
+                  for v in (r.L, r.M, r.N, r.i))
+    dot = np.clip(L[0] * L[1:] + M[0] * M[1:] + N[0] * N[1:], -1.0, 1.0)
+    na2 = (n * np.sin(np.arccos(dot))) ** 2
+    valid = i[1:] > 0
+    avg = float(np.mean(na2[valid] if valid.any() else na2))
+    fno = math.inf if avg <= 0 else 1 / (2 * math.sqrt(avg))
+    fno = min(fno, MAX_FNUM)
+    if math.isnan(fno):
+        raise ValueError("Working F/# could not be calculated due to raytrace errors.")
+    return fno
+
+
 class HuygensPSF:
     """Scalar Huygens-Fresnel PSF (psf/huygens_fresnel.py:31-348 `ScalarHuygensPSF`) for one
     field and wavelength: the pupil samples of the device wavefront (uniform grid, fp64)
@@ -368,7 +391,7 @@ class HuygensPSF:
     the ideal (zero-OPD, unit-amplitude) pupil.  Planar, unrotated image surfaces only: the
     drop-in (analysis_seams) takes its image points from the reference and covers the rest."""
 
-    MAX_FNUM = 10000.0  # utils.py:68
+    MAX_FNUM = MAX_FNUM
 
     def __init__(self, tracer, field, wavelength, num_rays: int = 128, image_size: int = 128,
                  strategy: str = "chief_ray", remove_tilt: bool = False, oversample=None,
@@ -413,23 +436,7 @@ class HuygensPSF:
 
     def working_fno(self) -> float:
         """utils.py:45-106 get_working_FNO: chief ray + four marginal rays."""
-        t = self.tracer
-        wl, _ = t._wavelength_index(self.wavelength)
-        n = float(t.table.optics[-1, wl]["n2"])
-        px = np.array([0.0, 0.0, 0.0, 1.0, -1.0])
-        py = np.array([0.0, 1.0, -1.0, 0.0, 0.0])
-        r = t.trace_generic(self.field[0], self.field[1], px, py, self.wavelength)
-        L, M, N, i = (torch.as_tensor(v).double().reshape(-1).cpu().numpy()
-                      for v in (r.L, r.M, r.N, r.i))
-        dot = np.clip(L[0] * L[1:] + M[0] * M[1:] + N[0] * N[1:], -1.0, 1.0)
-        na2 = (n * np.sin(np.arccos(dot))) ** 2
-        valid = i[1:] > 0
-        avg = float(np.mean(na2[valid] if valid.any() else na2))
-        fno = math.inf if avg <= 0 else 1 / (2 * math.sqrt(avg))
-        fno = min(fno, self.MAX_FNUM)
-        if math.isnan(fno):
-            raise ValueError("Working F/# could not be calculated due to raytrace errors.")
-        return fno
+        return working_fno(self.tracer, self.field, self.wavelength)
 
     def _get_image_extent(self):
         """huygens_fresnel.py:146-210."""
