@@ -855,6 +855,65 @@ int ol_geometric_mtf(ol_dtype dt, int32_t n_curves, const void* const* coords,
                      const double* scale, int32_t n_bins, double* mtf_out, int32_t* counts_out,
                      double* edges_minmax_out, int32_t* flags_out, void* stream);
 
+/* The Zernike decomposition of a sampled wavefront, its evaluation, and the sampled MTF
+ * (optiland/zernike/base.py:42-102 and 216-258, zernike/fit.py:101-118, wavefront/zernike_opd.py:
+ * 78-81, mtf/sampled.py:108-207; Niu & Tian, J. Opt. 24 (2022) 123001).  The basis is
+ *
+ *   Z_j(x, y) = norm_j R_n^|m|(r) (cos m phi for m >= 0, sin |m| phi for m < 0), phi = atan2(y, x)
+ *   R_n^|m|(r) = sum_k c_k r^(n - 2k),  c_k = (-1)^k (n-k)! / (k! ((n+|m|)/2-k)! ((n-|m|)/2-k)!)
+ *
+ * described by a TERM TABLE the host builds (optiland_amd/zernike.py `term_table`) and keeps on
+ * the DEVICE: term_i, num_terms x 4 int32 (output column j, n, m, number of radial coefficients
+ * s + 1 <= OL_ZK_MAX_RADIAL), and term_f, num_terms x (1 + OL_ZK_MAX_RADIAL) doubles (norm_j,
+ * c_0 ... c_s: highest power first, exact integers).  The rows are GROUPED by ascending |m|
+ * (|m| <= OL_ZK_MAX_M) and the columns are a permutation of 0 .. num_terms - 1; the kernels clamp
+ * what they read from the table, so a damaged one gives wrong numbers, never a wild access.  All
+ * other arrays are fp64 device arrays too.  At r = 0 every m != 0 term is 0.
+ *
+ * ol_zernike_fit: the least-squares coefficients of z over the n points (x, y) whose intensity is
+ * > 0 (intensity nullable: every point).  Normal equations in fp64 -- per-block partial Gram
+ * matrices merged in block order, Jacobi scaling, Cholesky -- and ONE step of iterative
+ * refinement with the residual z - A c formed per point.  Five launches; no floating-point
+ * atomics, fixed summation order: bit-identical from run to run.  status_out (one int32 on the
+ * device) is 0 or an OR of OL_ZK_TOO_FEW (fewer valid points than terms), OL_ZK_RANK_DEFICIENT
+ * (a scaled pivot <= 1e-8: rank deficient, or too ill-conditioned for normal equations) and
+ * OL_ZK_NONFINITE (a NaN or an infinity among the valid points); coeffs_out (num_terms doubles)
+ * is then NaN.  Stream-ordered workspace (hipMallocAsync).
+ *
+ * ol_zernike_eval: out[i] = sum_j coeffs[j] Z_j(x[i], y[i]), any r (no mask).
+ *
+ * ol_sampled_mtf: for each of the n_freq shift pairs (shifts[2 f], shifts[2 f + 1]), in
+ * normalised pupil units,
+ *
+ *   otf_f = sum_i P1_i sqrt(I_i) exp(-2 pi i W(x_i - dx_f, y_i - dy_f)) / sum_i I_i
+ *
+ * over the points whose shifted radius is <= 1, W the Zernike sum; P1_i = sqrt(I_i) exp(2 pi i
+ * opd_waves[i]), or the interleaved (re, im) pairs of `p1` when that is given (opd_waves may then
+ * be NULL).  mtf_out[f] = |otf_f|; otf_out (nullable) n_freq interleaved pairs; sum I = 0 gives
+ * 0.  The phase is carried in cycles and reduced exactly before the sincos.  Grid = (point
+ * chunks, frequencies), fixed-order partials and a finish pass: bit-identical from run to run.
+ *
+ * OL_EINVAL (checked before any device call): num_terms outside 1..OL_ZK_MAX_TERMS, n_freq
+ * outside 0..OL_SMTF_MAX_FREQ, a negative n or one above INT32_MAX, NULL arrays.            */
+#define OL_ZK_MAX_TERMS 120
+#define OL_ZK_MAX_RADIAL 12
+#define OL_ZK_MAX_M 32
+#define OL_ZK_TOO_FEW 1
+#define OL_ZK_RANK_DEFICIENT 2
+#define OL_ZK_NONFINITE 4
+#define OL_SMTF_MAX_FREQ 65535
+int ol_zernike_fit(int32_t num_terms, const int32_t* term_i, const double* term_f, int64_t n,
+                   const double* x, const double* y, const double* z, const double* intensity,
+                   double* coeffs_out, int32_t* status_out, void* stream);
+int ol_zernike_eval(int32_t num_terms, const int32_t* term_i, const double* term_f,
+                    const double* coeffs, int64_t n, const double* x, const double* y,
+                    double* out, void* stream);
+int ol_sampled_mtf(int32_t num_terms, const int32_t* term_i, const double* term_f,
+                   const double* coeffs, int64_t n, const double* x, const double* y,
+                   const double* opd_waves, const double* p1, const double* intensity,
+                   int32_t n_freq, const double* shifts, double* mtf_out, double* otf_out,
+                   void* stream);
+
 /* Profiling knobs (process-wide, not part of the trace semantics).
  *   OL_TUNE_RAYS_PER_THREAD  0 = auto (16-byte vector of rays per lane for conic-only
  *                            ranges, one ray per lane when Newton surfaces are

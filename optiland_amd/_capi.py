@@ -146,6 +146,9 @@ EXPORTS = (
     "ol_arena_free",
     "ol_huygens_psf",
     "ol_geometric_mtf",
+    "ol_zernike_fit",
+    "ol_zernike_eval",
+    "ol_sampled_mtf",
 )
 
 F32, F64 = 0, 1
@@ -285,7 +288,25 @@ def bind(lib, path: str = "?"):
         lib.ol_geometric_mtf.restype = C.c_int
         lib.ol_geometric_mtf.argtypes = [C.c_int, i32, C.POINTER(vp), C.POINTER(i64), i32, vp, vp,
                                          i32, vp, vp, vp, vp, vp]
+    if has_zernike_fit(lib):   # (additive within ABI 11: the three come together)
+        lib.ol_zernike_fit.restype = C.c_int
+        lib.ol_zernike_fit.argtypes = [i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+        lib.ol_zernike_eval.restype = C.c_int
+        lib.ol_zernike_eval.argtypes = [i32, vp, vp, vp, i64, vp, vp, vp, vp]
+        lib.ol_sampled_mtf.restype = C.c_int
+        lib.ol_sampled_mtf.argtypes = [i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp,
+                                       vp]
     return lib
+
+
+# OL_ZK_* / OL_SMTF_* (optiland_hip.h)
+ZK_MAX_TERMS, ZK_MAX_RADIAL, ZK_MAX_M, SMTF_MAX_FREQ = 120, 12, 32, 65535
+ZK_TOO_FEW, ZK_RANK_DEFICIENT, ZK_NONFINITE = 1, 2, 4
+
+
+def has_zernike_fit(lib) -> bool:
+    """True when the loaded library exports ol_zernike_fit, ol_zernike_eval and ol_sampled_mtf."""
+    return all(hasattr(lib, s) for s in ("ol_zernike_fit", "ol_zernike_eval", "ol_sampled_mtf"))
 
 
 MTF_MAX_CURVES, MTF_MAX_BINS, MTF_NONFINITE = 64, 8192, 1   # OL_MTF_* (optiland_hip.h)

@@ -25,7 +25,12 @@ for exactly that:
   pupil grid of an analysis in one launch instead of a Python loop over the rings (round 4:
   10 of the 11 ms of an OPD at 256 rings);
 * `GeometricMTF._generate_mtf_data` (mtf/geometric.py:152-177) -> `ol_geometric_mtf`: histogram
-  and transform of every field's two curves in three kernels.
+  and transform of every field's two curves in three kernels;
+* `ZernikeFit._fit` (zernike/fit.py:101-118) -> `ol_zernike_fit`: basis, normal equations,
+  Cholesky and one refinement step in five kernels instead of a few thousand tiny launches
+  before `lstsq` (`ZernikeOPD` and `SampledMTF` fit through it);
+* `SampledMTF.calculate_mtf` (mtf/sampled.py:108-207) -> `ol_sampled_mtf`: every frequency of
+  the call in two kernels (`MTFVsField`, `ThroughFocusMTF` are built on it).
 
 Every patched method first asks whether the call is one the fused path covers -- drop-in
 active for this optic, torch backend on the HIP device without autograd, a system the
@@ -54,7 +59,7 @@ STATS = {"spot": 0, "spot_fallback": 0, "ee": 0, "ee_fallback": 0, "opd": 0, "op
          "pupil": 0, "pupil_fallback": 0, "opd_init": 0, "opd_init_fallback": 0,
          "dist": 0, "dist_fallback": 0, "opd_fit": 0, "opd_fit_fallback": 0, "spot_grid": 0,
          "spot_radius": 0, "huygens": 0, "huygens_fallback": 0, "geo_mtf": 0,
-         "geo_mtf_fallback": 0}
+         "geo_mtf_fallback": 0, "zfit": 0, "zfit_fallback": 0, "smtf": 0, "smtf_fallback": 0}
 
 
 def _why(seam, reason):
@@ -1294,6 +1299,186 @@ def _geometric_mtf_device(self):
     return [[mtf[2 * k], mtf[2 * k + 1]] for k in range(len(self.data))], scale_factor
 
 
+# --------------------------------------------------------------------------- Zernike fit, sampled MTF
+def _grad_mode(be) -> bool:
+    try:
+        return bool(be._backends[be.get_backend()]._config.grad_mode.requires_grad)
+    except Exception:  # noqa: BLE001 - a backend without that configuration object
+        return False
+
+
+def _zernike_kind(zernike):
+    """'fringe' / 'standard' / 'noll' for an instance of exactly one of the reference's three
+    classes, else None (a subclass may override the basis or `poly`)."""
+    import optiland.zernike as oz
+
+    for kind, name in (("fringe", "ZernikeFringe"), ("standard", "ZernikeStandard"),
+                       ("noll", "ZernikeNoll")):
+        if type(zernike) is getattr(oz, name, None):
+            return kind
+    return None
+
+
+def _zk_ready(seam, be, tensors):
+    """The library when the call can be served: torch backend, every tensor on the HIP device,
+    no autograd, a library with the three entry points."""
+    from . import _capi
+
+    if be.get_backend() != "torch" or not torch.cuda.is_available():
+        _why(seam, "not the torch backend on a HIP device")
+        return None
+    if any(not isinstance(t, torch.Tensor) or t.device.type != "cuda" for t in tensors):
+        _why(seam, "an input lives off the HIP device")
+        return None
+    if _grad_mode(be) or any(t.requires_grad for t in tensors):
+        _why(seam, "autograd")
+        return None
+    try:
+        lib = _capi.load()
+    except _capi.HipExtensionError as exc:
+        _why(seam, str(exc))
+        return None
+    if not _capi.has_zernike_fit(lib):
+        _why(seam, "library without ol_zernike_fit")
+        return None
+    return lib
+
+
+def _zernike_fit_fit(self):
+    """zernike/fit.py:101-118 (`ZernikeFit._fit`) with `ol_zernike_fit` on `self.x / y / z`: one
+    read-back, the status word.  `self.zernike.coeffs` ends up a device tensor of the backend's
+    dtype, as in the reference.  Falls back to the reference's method -- whose `lstsq` gives the
+    minimum-norm answer -- off the HIP device, under autograd, for tensors other than fp64, a
+    Zernike class that is not one of the reference's three, more than ZK_MAX_TERMS terms, and
+    when the status word says rank deficient, too few points or non-finite."""
+    out = _zernike_fit_device(self)
+    if out is None:
+        STATS["zfit_fallback"] += 1
+        return _ORIG["zfit"](self)
+    STATS["zfit"] += 1
+    self.zernike.coeffs = out
+    return None
+
+
+def _zernike_fit_device(self):
+    import optiland.backend as be
+
+    from . import _capi
+
+    tensors = [self.x, self.y, self.z]
+    if _zk_ready("zfit", be, tensors) is None:
+        return None
+    if any(t.dtype != torch.float64 or t.ndim != 1 for t in tensors):
+        _why("zfit", "x / y / z are not one-dimensional fp64 tensors")
+        return None
+    kind = _zernike_kind(self.zernike)
+    if kind is None:
+        _why("zfit", f"{type(self.zernike).__name__} is not a stock Zernike class")
+        return None
+    num_terms = len(self.zernike.coeffs)
+    if not 1 <= num_terms <= _capi.ZK_MAX_TERMS:
+        _why("zfit", f"{num_terms} terms")
+        return None
+    from .engine import zernike_fit
+
+    coeffs, status = zernike_fit(*[t.detach() for t in tensors], kind, num_terms,
+                                 device=self.x.device)
+    status = int(status)   # the ONE read-back
+    if status:
+        _why("zfit", f"status {status}")
+        return None
+    return coeffs.to(self.z.dtype)
+
+
+def _sampled_mtf_calculate(self, frequencies):
+    """mtf/sampled.py:108-207 (`SampledMTF.calculate_mtf`) with `ol_sampled_mtf`: all frequencies
+    of the call in one launch pair instead of a Python loop that rebuilds the Zernike basis per
+    frequency.  Everything is read at call time -- `zernike_fit.zernike` (type and current
+    coefficients), `P1`, `intensity`, `x_norm`, `y_norm`, `xpd`, `xpl`, `wavelength` -- so a user
+    who replaced any of them gets what they set.  Returns the reference's shape: a list with one
+    entry per frequency (0-d device tensors).  Falls back to the reference's method for
+    `xpd == 0`, under autograd, off the HIP device, for a Zernike object that is not one of the
+    reference's three classes (it may override `poly`), and for non-scalar frequencies."""
+    out = _sampled_mtf_device(self, frequencies)
+    if out is None:
+        STATS["smtf_fallback"] += 1
+        return _ORIG["smtf"](self, frequencies)
+    STATS["smtf"] += 1
+    return out
+
+
+def _scalar_pairs(frequencies):
+    """[(fx, fy), ...] as floats, or None when an entry is not a pair of scalars."""
+    if isinstance(frequencies, torch.Tensor):
+        if frequencies.ndim != 2 or frequencies.shape[1] != 2 or frequencies.is_complex():
+            return None
+        frequencies = frequencies.detach().cpu().tolist()
+    pairs = []
+    try:
+        for pair in frequencies:
+            fx, fy = pair
+            for v in (fx, fy):
+                if isinstance(v, (torch.Tensor, np.ndarray)) and v.ndim != 0:
+                    return None
+            pairs.append((float(fx), float(fy)))
+    except (TypeError, ValueError):
+        return None
+    return pairs
+
+
+def _sampled_mtf_device(self, frequencies):
+    import optiland.backend as be
+
+    from . import _capi
+
+    try:
+        zernike = self.zernike_fit.zernike
+        coeffs = zernike.coeffs
+        tensors = [coeffs, self.P1, self.intensity, self.x_norm, self.y_norm]
+    except AttributeError:
+        _why("smtf", "not the attributes of sampled.py")
+        return None
+    if _zk_ready("smtf", be, tensors) is None:
+        return None
+    if any(isinstance(v, torch.Tensor) and v.requires_grad for v in (self.xpd, self.xpl)):
+        _why("smtf", "autograd")
+        return None
+    kind = _zernike_kind(zernike)
+    if kind is None:
+        _why("smtf", f"{type(zernike).__name__} is not a stock Zernike class")
+        return None
+    if not 1 <= coeffs.numel() <= _capi.ZK_MAX_TERMS or coeffs.ndim != 1 or coeffs.is_complex():
+        _why("smtf", f"coefficients of shape {tuple(coeffs.shape)}")
+        return None
+    n = self.x_norm.numel()
+    if any(t.numel() != n for t in tensors[1:]) or self.intensity.is_complex() \
+            or self.x_norm.is_complex() or self.y_norm.is_complex():
+        _why("smtf", "pupil arrays of different sizes")
+        return None
+    pairs = _scalar_pairs(frequencies)
+    if pairs is None or len(pairs) > _capi.SMTF_MAX_FREQ:
+        _why("smtf", "non-scalar frequencies")
+        return None
+    xpd, xpl = _f(self.xpd), _f(self.xpl)
+    if xpd == 0.0:
+        _why("smtf", "xpd == 0")
+        return None
+    if not pairs:
+        return []
+    # sampled.py:158-178, the reference's operations in its order, in fp64 on the host
+    wl_mm = _f(self.wavelength) * 1e-3
+    shifts = xpl * (wl_mm * np.asarray(pairs, dtype=np.float64)) / (xpd / 2)
+    from .engine import sampled_mtf
+
+    p1 = self.P1.detach()
+    mtf = sampled_mtf(coeffs.detach(), kind, self.x_norm.detach(), self.y_norm.detach(), None,
+                      self.intensity.detach(), shifts,
+                      p1=p1 if p1.is_complex() else p1.to(torch.complex128),
+                      device=self.x_norm.device)
+    real = self.intensity.dtype if self.intensity.is_floating_point() else torch.float64
+    return list(mtf.to(real))
+
+
 # --------------------------------------------------------------------------- (de)activate
 # The seams replace PRIVATE methods of the reference.  Each entry: key in _ORIG -> (module,
 # class, method, the parameter names the replacement was written against, replacement).  A
@@ -1342,6 +1527,9 @@ _SEAMS = {
                 ("self",) + _HUYGENS_ARGS, "_huygens_torch_compute"),
     "geo_mtf": ("optiland.mtf.geometric", "GeometricMTF", "_generate_mtf_data", ("self",),
                 "_geometric_mtf_generate"),
+    "zfit": ("optiland.zernike.fit", "ZernikeFit", "_fit", ("self",), "_zernike_fit_fit"),
+    "smtf": ("optiland.mtf.sampled", "SampledMTF", "calculate_mtf", ("self", "frequencies"),
+             "_sampled_mtf_calculate"),
 }
 def _constructor_scope(key):
     """A constructor of the reference that only READS its optic -- `Wavefront.__init__`

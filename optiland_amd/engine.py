@@ -1724,3 +1724,165 @@ def geometric_mtf(coords, freq, scale=None, n_bins=None, want_counts=False, *, d
         raise ValueError(f"autodetected range of curve {bad[0]} is not finite "
                          "(a NaN or an infinite coordinate)")
     return (mtf, counts, edges) if want_counts else mtf
+
+
+_ZK_TABLES: dict = {}
+
+
+def _zk_library():
+    lib = _capi.load()
+    if not _capi.has_zernike_fit(lib):
+        raise _capi.HipExtensionError(
+            f"{_capi.library_path()} has no ol_zernike_fit / ol_zernike_eval / ol_sampled_mtf; "
+            "rebuild the library (`python -c 'import __graft_entry__ as g; g.build()'`)")
+    return lib
+
+
+def _zk_table(kind: str, num_terms: int, dev):
+    """The term table of (kind, num_terms) on `dev` (uploaded once per device)."""
+    from . import zernike as Z
+
+    key = (kind, num_terms, str(dev))
+    got = _ZK_TABLES.get(key)
+    if got is None:
+        ti, tf = Z.term_table(kind, num_terms)
+        got = (torch.from_numpy(ti.copy()).to(dev), torch.from_numpy(tf.copy()).to(dev))
+        _ZK_TABLES[key] = got
+    return got
+
+
+def _zk_shape(v):
+    return tuple(v.shape) if hasattr(v, "shape") else tuple(np.shape(v))
+
+
+def _zk_real(who, name, v):
+    if isinstance(v, torch.Tensor) and (v.is_complex() or not v.is_floating_point()):
+        raise ValueError(f"{who}: {name} must be real floating point, got {v.dtype}")
+
+
+def _zk_points(who, names, arrays):
+    """Host-side checks of same-sized real point arrays (nothing here touches a device): n."""
+    sizes = []
+    for name, v in zip(names, arrays):
+        _zk_real(who, name, v)
+        sizes.append(int(np.prod(_zk_shape(v), dtype=np.int64)))
+    if any(s != sizes[0] for s in sizes):
+        raise ValueError(f"{who}: " + " / ".join(names) + f" differ in size ({sizes})")
+    return sizes[0]
+
+
+def _zk_plane(v, dev):
+    return torch.as_tensor(v, device=dev).detach().to(torch.float64).reshape(-1).contiguous()
+
+
+def zernike_fit(x, y, z, kind: str = "fringe", num_terms: int = 37, intensity=None, *,
+                device=None):
+    """`ol_zernike_fit`: the least-squares Zernike coefficients of z over the points (x, y)
+    (zernike/fit.py:101-118), fp64 on the device.  `kind`: 'fringe', 'standard' or 'noll';
+    `intensity` (optional): points with intensity <= 0 are left out (zernike_opd.py:78-81),
+    without boolean indexing.  Returns (coeffs (num_terms,) float64 device tensor, status (1,)
+    int32 DEVICE tensor): 0, or an OR of `_capi.ZK_TOO_FEW`, `ZK_RANK_DEFICIENT`, `ZK_NONFINITE`,
+    in which case the coefficients are NaN.  No read-back here."""
+    from . import zernike as Z
+
+    num_terms = Z.check_terms(kind, num_terms, "zernike_fit")
+    names, arrays = ["x", "y", "z"], [x, y, z]
+    if intensity is not None:
+        names.append("intensity")
+        arrays.append(intensity)
+    n = _zk_points("zernike_fit", names, arrays)
+    lib = _zk_library()
+    dev = _require_gpu(device)
+    planes = [_zk_plane(v, dev) for v in arrays]
+    ti, tf = _zk_table(kind, num_terms, dev)
+    coeffs = torch.empty(num_terms, dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.ol_zernike_fit(num_terms, ti.data_ptr(), tf.data_ptr(), n,
+                                *[p.data_ptr() if n else None for p in planes[:3]],
+                                planes[3].data_ptr() if intensity is not None and n else None,
+                                coeffs.data_ptr(), status.data_ptr(), _stream_ptr(dev))
+    _capi.check(rc, "ol_zernike_fit", lib)
+    return coeffs, status
+
+
+def _zk_coeffs(who, coeffs, kind):
+    from . import zernike as Z
+
+    _zk_real(who, "coeffs", coeffs)
+    shape = _zk_shape(coeffs)
+    if len(shape) != 1:
+        raise ValueError(f"{who}: coeffs must be one-dimensional, got shape {shape}")
+    return Z.check_terms(kind, shape[0], who)
+
+
+def zernike_eval(coeffs, kind: str, x, y, *, device=None):
+    """`ol_zernike_eval`: sum_j coeffs[j] Z_j(x, y) at Cartesian points of any radius (no mask),
+    float64, x's shape.  The number of terms is that of `coeffs`."""
+    num_terms = _zk_coeffs("zernike_eval", coeffs, kind)
+    n = _zk_points("zernike_eval", ["x", "y"], [x, y])
+    shape = _zk_shape(x)
+    lib = _zk_library()
+    dev = _require_gpu(device)
+    c = _zk_plane(coeffs, dev)
+    px, py = _zk_plane(x, dev), _zk_plane(y, dev)
+    ti, tf = _zk_table(kind, num_terms, dev)
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    if n:
+        with torch.cuda.device(dev):
+            rc = lib.ol_zernike_eval(num_terms, ti.data_ptr(), tf.data_ptr(), c.data_ptr(), n,
+                                     px.data_ptr(), py.data_ptr(), out.data_ptr(),
+                                     _stream_ptr(dev))
+        _capi.check(rc, "ol_zernike_eval", lib)
+    return out.reshape(shape)
+
+
+def sampled_mtf(coeffs, kind: str, x, y, opd_waves, intensity, shifts, *, p1=None,
+                want_otf: bool = False, device=None):
+    """`ol_sampled_mtf`: the overlap sum of mtf/sampled.py:162-205 for ALL frequencies in one call.
+
+    coeffs / kind: the Zernike fit of the wavefront; x, y: normalised pupil coordinates;
+    opd_waves, intensity: the samples; shifts: (F, 2) pupil shifts (dx, dy) in normalised pupil
+    units (sampled.py:170-178).  `p1` (optional, complex): the pupil function to use instead of
+    sqrt(intensity) exp(2 pi i opd_waves) -- `opd_waves` may then be None.  Returns mtf, a (F,)
+    float64 device tensor, or with `want_otf` (mtf, otf complex128)."""
+    num_terms = _zk_coeffs("sampled_mtf", coeffs, kind)
+    names, arrays = ["x", "y", "intensity"], [x, y, intensity]
+    if opd_waves is not None:
+        names.append("opd_waves")
+        arrays.append(opd_waves)
+    elif p1 is None:
+        raise ValueError("sampled_mtf: neither opd_waves nor p1 is given")
+    n = _zk_points("sampled_mtf", names, arrays)
+    if p1 is not None and int(np.prod(_zk_shape(p1), dtype=np.int64)) != n:
+        raise ValueError(f"sampled_mtf: p1 has {_zk_shape(p1)} entries, x {n}")
+    _zk_real("sampled_mtf", "shifts", shifts)
+    sshape = _zk_shape(shifts)
+    if len(sshape) != 2 or sshape[1] != 2:
+        raise ValueError(f"sampled_mtf: shifts must have shape (F, 2), got {sshape}")
+    n_freq = int(sshape[0])
+    if n_freq > _capi.SMTF_MAX_FREQ:
+        raise ValueError(f"sampled_mtf: {n_freq} frequencies, at most {_capi.SMTF_MAX_FREQ}")
+    lib = _zk_library()
+    dev = _require_gpu(device)
+    c = _zk_plane(coeffs, dev)
+    planes = [_zk_plane(v, dev) for v in arrays]
+    opd = planes[3] if opd_waves is not None else None
+    pupil = None
+    if p1 is not None:
+        pupil = torch.view_as_real(torch.as_tensor(p1, device=dev).detach().to(torch.complex128)
+                                   .reshape(-1).contiguous())
+    sh = torch.as_tensor(shifts, device=dev).detach().to(torch.float64).contiguous()
+    ti, tf = _zk_table(kind, num_terms, dev)
+    mtf = torch.empty(n_freq, dtype=torch.float64, device=dev)
+    otf = torch.empty(n_freq, dtype=torch.complex128, device=dev) if want_otf else None
+    if n_freq:
+        ptr = lambda t: t.data_ptr() if t is not None and n else None  # noqa: E731
+        with torch.cuda.device(dev):
+            rc = lib.ol_sampled_mtf(num_terms, ti.data_ptr(), tf.data_ptr(), c.data_ptr(), n,
+                                    ptr(planes[0]), ptr(planes[1]), ptr(opd), ptr(pupil),
+                                    ptr(planes[2]), n_freq, sh.data_ptr(), mtf.data_ptr(),
+                                    otf.data_ptr() if otf is not None else None,
+                                    _stream_ptr(dev))
+        _capi.check(rc, "ol_sampled_mtf", lib)
+    return (mtf, otf) if want_otf else mtf

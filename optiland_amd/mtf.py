@@ -9,6 +9,10 @@ Python loop over the frequencies.  The numbers are those of the reference's NumP
 
 `FFTMTF` mirrors `ScalarFFTMTF` (optiland/mtf/fft.py:19-235) on top of `wavefront.FFTPSF` and
 `torch.fft`; no kernel of its own.
+
+`SampledMTF` mirrors the reference's fast MTF (optiland/mtf/sampled.py:17-207): the fused OPD map,
+its Zernike fit (`ol_zernike_fit`) and the overlap sums of ALL requested frequencies in one
+`ol_sampled_mtf` call instead of a Python loop that re-evaluates the basis per frequency.
 """
 
 from __future__ import annotations
@@ -16,7 +20,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .wavefront import FFTPSF, calculate_grid_size, working_fno
+from .wavefront import FFTPSF, Wavefront, calculate_grid_size, working_fno
 
 
 def _resolve_fields(table, fields):
@@ -202,3 +206,88 @@ class FFTMTF:
     def _units_tang(self, k) -> float:
         """fft.py:196-218: the chief ray's tilt compresses the tangential axis."""
         return self._units_sag(k) * (self._on_axis_fno / self.FNO[k])
+
+
+def paraxial_exit_pupil(table):
+    """(XPD, XPL) of `optic.paraxial` (paraxial.py:244-275) from the packed table: XPL is the
+    exit-pupil position the table carries, relative to the image surface; XPD twice the height
+    of the paraxial marginal ray (paraxial.py:316-345, restated in paraxial_host) there."""
+    from . import paraxial_host
+    from . import system as S
+
+    surf, rg = table.surfaces, table.raygen
+    wi = table.reference_wavelength_index()
+    n = [float(v) for v in table.optics[:, wi]["n2"]]
+    pos = [float(v) for v in surf["origin"][:, 2]]
+    reflect = (surf["interaction"] == S.INTERACT_REFLECT).tolist()
+    radii = [float(r) for r in surf["radius"]]
+    xpl = float(rg["pupil_z"]) - pos[-1]
+    epd = float(rg["EPD"])
+    if rg.get("object_infinite"):
+        ya, ua, z0 = epd / 2, 0.0, pos[1] - 10.0
+    else:
+        z0 = pos[0]
+        ya, ua = 0.0, epd / (2 * (float(rg["EPL"]) - z0))
+    y, u = paraxial_host._trace(radii, n, pos, reflect, ya, ua, z0)
+    return 2 * (y[-1] + u[-1] * xpl), xpl
+
+
+def pupil_shifts(frequencies, wavelength_um: float, xpd: float, xpl: float) -> np.ndarray:
+    """sampled.py:158-178: the (F, 2) pupil shifts, in normalised pupil units, of spatial
+    frequencies (fx, fy) in cycles / mm; `xpl` is the class's attribute (minus the paraxial
+    XPL).  The operations and their order are the reference's."""
+    wl_mm = wavelength_um * 1e-3
+    f = np.asarray(frequencies, dtype=np.float64).reshape(-1, 2)
+    return xpl * (wl_mm * f) / (xpd / 2)
+
+
+class SampledMTF:
+    """The sampled MTF (mtf/sampled.py:17-207) of one field and wavelength: same arguments and
+    attributes as the reference -- `x_norm`, `y_norm`, `opd_waves`, `intensity` (float64 device
+    tensors), `xpd`, `xpl`, `zernike_coeffs` (the fit of the OPD map over every sample, as
+    sampled.py:97-103 fits it), `otf_at_zero`.  `calculate_mtf(frequencies)` returns a list
+    with one entry per (fx, fy) pair in cycles / mm: views of ONE device tensor, `mtf_all`."""
+
+    def __init__(self, tracer, field, wavelength, num_rays: int = 128,
+                 distribution: str = "uniform", zernike_terms: int = 37,
+                 zernike_type: str = "fringe"):
+        from . import zernike as Z
+
+        self.zernike_terms = Z.check_terms(zernike_type, zernike_terms, "SampledMTF")
+        self.zernike_type = zernike_type
+        self.tracer, self.field = tracer, field
+        self.wavelength = _resolve_wavelength(tracer.table, wavelength)
+        self.num_rays, self.distribution = num_rays, distribution
+        wf = Wavefront(tracer, field, self.wavelength, num_rays=num_rays,
+                       distribution=distribution)
+        self.x_norm, self.y_norm = tracer._dev(wf.distribution.x), tracer._dev(wf.distribution.y)
+        self.opd_waves, self.intensity = wf.data.opd, wf.data.intensity
+        xpd, xpl = paraxial_exit_pupil(tracer.table)
+        self.xpd, self.xpl = xpd, -xpl
+        self.zernike_coeffs, status = self._fit()
+        if status:
+            raise ValueError(f"SampledMTF: {Z.status_text(status)}")
+        self.otf_at_zero = self.intensity.sum()
+
+    def _fit(self):
+        from .engine import zernike_fit
+
+        c, status = zernike_fit(self.x_norm, self.y_norm, self.opd_waves, self.zernike_type,
+                                self.zernike_terms, device=self.tracer.device)
+        return c, int(status)
+
+    def _sum(self, shifts):
+        from .engine import sampled_mtf
+
+        return sampled_mtf(self.zernike_coeffs, self.zernike_type, self.x_norm, self.y_norm,
+                           self.opd_waves, self.intensity, shifts, device=self.tracer.device)
+
+    def calculate_mtf(self, frequencies):
+        """sampled.py:108-207."""
+        freq = [(float(fx), float(fy)) for fx, fy in frequencies]
+        if self.xpd == 0.0:   # sampled.py:163-168
+            return [1.0 if fx == 0.0 and fy == 0.0 else 0.0 for fx, fy in freq]
+        if not freq:
+            return []
+        self.mtf_all = self._sum(pupil_shifts(freq, self.wavelength, self.xpd, self.xpl))
+        return list(self.mtf_all)

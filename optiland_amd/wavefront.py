@@ -299,6 +299,47 @@ class OPD(Wavefront):
         return float(torch.sqrt(torch.mean(o * o)))
 
 
+class ZernikeOPD(OPD):
+    """wavefront/zernike_opd.py:18-83: the Zernike decomposition of the OPD map over a hexapolar
+    pupil, on the fused OPD of any of the three strategies and `ol_zernike_fit`.  Rays with
+    intensity <= 0 are left out by the KERNEL (the reference's `mask`, without boolean indexing
+    or a read-back).  `coeffs` (num_terms,) float64 device tensor, `poly(x, y)`, `indices`,
+    `zernike_type`, `num_terms`; `x`, `y`, `z`: the fitted samples (all of them: the mask is
+    `data.intensity > 0`)."""
+
+    def __init__(self, tracer, field, wavelength, num_rings: int = 15,
+                 zernike_type: str = "fringe", num_terms: int = 37, strategy: str = "chief_ray",
+                 remove_tilt: bool = False, **kwargs):
+        from . import zernike as Z
+
+        self.num_terms = Z.check_terms(zernike_type, num_terms, "ZernikeOPD")
+        self.zernike_type = zernike_type
+        self.indices = Z.indices(zernike_type, self.num_terms)
+        super().__init__(tracer, field, wavelength, num_rays=num_rings,
+                         distribution="hexapolar", strategy=strategy, remove_tilt=remove_tilt,
+                         **kwargs)
+        self.x, self.y = tracer._dev(self.distribution.x), tracer._dev(self.distribution.y)
+        self.z = self.data.opd
+        self.num_pts = int(self.z.numel())
+        self.coeffs, self.status = self._fit()
+        if self.status:
+            raise ValueError(f"ZernikeOPD: {Z.status_text(self.status)}")
+
+    def _fit(self):
+        """(coeffs, status): one `ol_zernike_fit` call and ONE read-back, the status word."""
+        from .engine import zernike_fit
+
+        c, status = zernike_fit(self.x, self.y, self.z, self.zernike_type, self.num_terms,
+                                intensity=self.data.intensity, device=self.z.device)
+        return c, int(status)
+
+    def poly(self, x, y):
+        """The fitted wavefront at normalised pupil points (`ol_zernike_eval`), in waves."""
+        from .engine import zernike_eval
+
+        return zernike_eval(self.coeffs, self.zernike_type, x, y, device=self.coeffs.device)
+
+
 def calculate_grid_size(num_rays: int) -> tuple[int, int]:
     """psf/fft.py:20-39."""
     eff = int(np.floor(32 * 2 ** ((np.log2(num_rays) - 5) / 2)))

@@ -1,0 +1,401 @@
+"""The Zernike fit and the sampled MTF without a GPU: the argument rules of the three entry
+points and of their torch wrappers (checked before any device is touched), the binding of a
+library without the symbols, the host index / norm / coefficient tables against the reference's
+(tests/golden/zernike_fit.npz), the host logic of the stand-alone classes with NumPy stand-ins
+for the kernels, and the installation and fall-backs of the two seams on stand-in modules."""
+
+import math
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from optiland_amd import _capi, build, engine, load_system
+from optiland_amd import mtf as mtf_mod
+from optiland_amd import tracer as tr
+from optiland_amd import zernike as Z
+from optiland_amd.mtf import SampledMTF
+from optiland_amd.wavefront import ZernikeOPD
+from tests import _zernike_fit as M
+
+GOLD = M.golden()
+
+
+@pytest.fixture(scope="module")
+def lib():
+    build.build_library()
+    return _capi.load()
+
+
+# ------------------------------------------------------------------ the C entry points
+def test_the_library_exports_the_three_entry_points(lib):
+    assert _capi.has_zernike_fit(lib)
+    for name in ("ol_zernike_fit", "ol_zernike_eval", "ol_sampled_mtf"):
+        assert name in _capi.EXPORTS and hasattr(lib, name)
+    assert _capi.ZK_MAX_TERMS >= 120 and _capi.ABI_VERSION == 11
+
+
+def test_argument_validation_without_a_device(lib):
+    p = 16      # never dereferenced: every call must fail first
+
+    def fit(k=37, ti=p, tf=p, n=8, x=p, y=p, z=p, c=p, st=p):
+        return lib.ol_zernike_fit(k, ti, tf, n, x, y, z, None, c, st, None)
+
+    for k in (0, -1, _capi.ZK_MAX_TERMS + 1):
+        assert fit(k=k) == -1 and b"num_terms" in lib.ol_last_error()
+    assert b"OL_ZK_MAX_TERMS" in lib.ol_last_error()
+    assert fit(ti=None) == -1 and b"term table" in lib.ol_last_error()
+    assert fit(tf=None) == -1 and b"term table" in lib.ol_last_error()
+    assert fit(n=-1) == -1 and b"negative count" in lib.ol_last_error()
+    assert fit(n=2 ** 31) == -1 and b"INT32_MAX" in lib.ol_last_error()
+    assert fit(c=None) == -1 and b"coeffs_out" in lib.ol_last_error()
+    assert fit(st=None) == -1 and b"status_out" in lib.ol_last_error()
+    for hole in ("x", "y", "z"):
+        assert fit(**{hole: None}) == -1 and b"x / y / z" in lib.ol_last_error()
+
+    def ev(k=37, ti=p, tf=p, c=p, n=8, x=p, y=p, out=p):
+        return lib.ol_zernike_eval(k, ti, tf, c, n, x, y, out, None)
+
+    assert ev(k=_capi.ZK_MAX_TERMS + 1) == -1 and b"num_terms" in lib.ol_last_error()
+    assert ev(ti=None) == -1 and b"term table" in lib.ol_last_error()
+    assert ev(c=None) == -1 and b"coeffs" in lib.ol_last_error()
+    assert ev(n=-3) == -1 and b"negative count" in lib.ol_last_error()
+    assert ev(out=None) == -1 and b"out" in lib.ol_last_error()
+    assert ev(n=0, x=None, y=None, out=None) == 0      # nothing to do: no device needed
+
+    def mtf(k=37, ti=p, tf=p, c=p, n=8, x=p, y=p, opd=p, p1=None, inten=p, f=4, sh=p, out=p):
+        return lib.ol_sampled_mtf(k, ti, tf, c, n, x, y, opd, p1, inten, f, sh, out, None, None)
+
+    assert mtf(k=0) == -1 and b"num_terms" in lib.ol_last_error()
+    assert mtf(tf=None) == -1 and b"term table" in lib.ol_last_error()
+    assert mtf(n=-1) == -1 and b"negative count" in lib.ol_last_error()
+    for f in (-1, _capi.SMTF_MAX_FREQ + 1):
+        assert mtf(f=f) == -1 and b"n_freq" in lib.ol_last_error()
+    assert mtf(c=None) == -1 and b"coeffs" in lib.ol_last_error()
+    assert mtf(sh=None) == -1 and b"shifts" in lib.ol_last_error()
+    assert mtf(out=None) == -1 and b"mtf_out" in lib.ol_last_error()
+    assert mtf(inten=None) == -1 and b"intensity" in lib.ol_last_error()
+    assert mtf(opd=None) == -1 and b"neither opd_waves nor p1" in lib.ol_last_error()
+    assert mtf(f=0, sh=None, out=None) == 0            # nothing to do: no device needed
+
+
+def test_engine_checks_its_arguments_before_the_device(monkeypatch):
+    def no_device(*a, **k):
+        raise AssertionError("the device was asked for")
+
+    monkeypatch.setattr(engine, "_require_gpu", no_device)
+    monkeypatch.setattr(_capi, "load", no_device)
+    x = np.zeros(50)
+    with pytest.raises(ValueError, match="ZK_MAX_TERMS"):
+        engine.zernike_fit(x, x, x, "fringe", _capi.ZK_MAX_TERMS + 1)
+    with pytest.raises(ValueError, match="num_terms"):
+        engine.zernike_fit(x, x, x, "fringe", 0)
+    with pytest.raises(ValueError, match="integer"):
+        engine.zernike_fit(x, x, x, "fringe", 3.5)
+    with pytest.raises(ValueError, match="Invalid Zernike type"):
+        engine.zernike_fit(x, x, x, "zemax", 10)
+    with pytest.raises(ValueError, match="differ in size"):
+        engine.zernike_fit(x, x[:-1], x, "noll", 10)
+    with pytest.raises(ValueError, match="differ in size"):
+        engine.zernike_fit(x, x, x, "noll", 10, intensity=x[:3])
+    with pytest.raises(ValueError, match="floating point"):
+        engine.zernike_fit(x, x, torch.zeros(50, dtype=torch.complex128), "noll", 10)
+    with pytest.raises(ValueError, match="one-dimensional"):
+        engine.zernike_eval(np.zeros((2, 5)), "fringe", x, x)
+    with pytest.raises(ValueError, match="ZK_MAX_TERMS"):
+        engine.zernike_eval(np.zeros(_capi.ZK_MAX_TERMS + 1), "fringe", x, x)
+    with pytest.raises(ValueError, match="differ in size"):
+        engine.zernike_eval(np.zeros(4), "fringe", x, x[:7])
+    c, sh = np.zeros(37), np.zeros((3, 2))
+    with pytest.raises(ValueError, match=r"\(F, 2\)"):
+        engine.sampled_mtf(c, "fringe", x, x, x, x, np.zeros(6))
+    with pytest.raises(ValueError, match="differ in size"):
+        engine.sampled_mtf(c, "fringe", x, x, x[:4], x, sh)
+    with pytest.raises(ValueError, match="neither opd_waves nor p1"):
+        engine.sampled_mtf(c, "fringe", x, x, None, x, sh)
+    with pytest.raises(ValueError, match="p1"):
+        engine.sampled_mtf(c, "fringe", x, x, None, x, sh, p1=np.zeros(4, dtype=complex))
+    with pytest.raises(ValueError, match="Invalid Zernike type"):
+        engine.sampled_mtf(c, "ansi", x, x, x, x, sh)
+
+
+class _Symbol:
+    restype = argtypes = None
+
+    def __call__(self, *a):
+        return _capi.ABI_VERSION
+
+
+class _OlderLibrary:
+    """What ctypes shows of a build that predates the three entry points."""
+
+    def __getattr__(self, name):
+        if name in _capi.EXPORTS and name not in ("ol_zernike_fit", "ol_zernike_eval",
+                                                  "ol_sampled_mtf"):
+            fn = _Symbol()
+            setattr(self, name, fn)
+            return fn
+        raise AttributeError(name)
+
+
+def test_a_library_without_the_entry_points_binds_and_asks_for_a_rebuild(monkeypatch):
+    old = _OlderLibrary()
+    assert _capi.bind(old, "older.so") is old          # additive within ABI 11: no complaint
+    assert not _capi.has_zernike_fit(old) and _capi.has_geometric_mtf(old)
+    monkeypatch.setattr(_capi, "load", lambda: old)
+    x = np.zeros(12)
+    for call in (lambda: engine.zernike_fit(x, x, x, "fringe", 4),
+                 lambda: engine.zernike_eval(np.zeros(4), "fringe", x, x),
+                 lambda: engine.sampled_mtf(np.zeros(4), "fringe", x, x, x, x, np.zeros((2, 2)))):
+        with pytest.raises(_capi.HipExtensionError, match="rebuild"):
+            call()
+
+
+# ------------------------------------------------------------------ the host tables
+@pytest.mark.parametrize("kind", Z.KINDS)
+def test_index_and_norm_tables_match_the_reference(kind):
+    want = GOLD[f"indices/{kind}"]
+    assert want.shape == (120, 2) and _capi.ZK_MAX_TERMS >= 120
+    for k in (1, 2, 4, 36, 37, 64, 119, 120):
+        assert np.array_equal(np.array(Z.indices(kind, k)), want[:k]), (kind, k)
+    norms = np.array([Z.norm_constant(kind, n, m) for n, m in Z.indices(kind, 120)])
+    assert np.allclose(norms, GOLD[f"norms/{kind}"], rtol=2 ** -52, atol=0)
+    with pytest.raises(ValueError, match="ZK_MAX_TERMS"):
+        Z.indices(kind, _capi.ZK_MAX_TERMS + 1)
+    with pytest.raises(ValueError, match="Invalid Zernike type"):
+        Z.indices("arizona", 4)
+
+
+@pytest.mark.parametrize("kind", Z.KINDS)
+def test_term_table(kind):
+    k = _capi.ZK_MAX_TERMS
+    ti, tf = Z.term_table(kind, k)
+    assert ti.shape == (k, 4) and ti.dtype == np.int32
+    assert tf.shape == (k, 1 + _capi.ZK_MAX_RADIAL) and tf.dtype == np.float64
+    assert sorted(ti[:, 0].tolist()) == list(range(k))           # a permutation of the columns
+    assert np.all(np.diff(np.abs(ti[:, 2])) >= 0)                # grouped by ascending |m|
+    assert np.abs(ti[:, 2]).max() <= _capi.ZK_MAX_M
+    idx = Z.indices(kind, k)
+    f = math.factorial
+    for (col, n, m, nc), row in zip(ti.tolist(), tf):
+        assert (n, m) == idx[col] and nc == (n - abs(m)) // 2 + 1 <= _capi.ZK_MAX_RADIAL
+        assert row[0] == Z.norm_constant(kind, n, m)
+        a = abs(m)
+        for j in range(nc):      # exact integers, as exact doubles
+            want = (-1) ** j * f(n - j) // (f(j) * f((n + a) // 2 - j) * f((n - a) // 2 - j))
+            assert row[1 + j] == want and int(row[1 + j]) == want
+        assert np.all(row[1 + nc:] == 0.0)
+        assert math.isclose(sum(row[1:1 + nc]), 1.0, abs_tol=0)  # R_n^|m|(1) = 1
+
+
+@pytest.mark.parametrize("case", M.names(GOLD, "fit_cases"))
+def test_host_basis_reproduces_the_reference_fit(case):
+    """`zernike.basis_numpy` -- the kernels' arithmetic restated on the host -- and `lstsq`."""
+    x, y, z, kind, k = M.fit_inputs(GOLD, case)
+    got, cond = M.numpy_fit(x, y, z, kind, k)
+    want = GOLD[f"{case}/coeffs"]
+    assert cond == pytest.approx(float(GOLD[f"{case}/cond"]), rel=1e-9)
+    assert float(np.abs(got - want).max()) <= M.fit_bound(GOLD[f"{case}/spread"], cond, k,
+                                                          np.abs(want).max())
+
+
+def test_host_basis_at_the_origin_and_on_the_rim():
+    for kind in Z.KINDS:
+        A = Z.basis_numpy(kind, 37, [0.0, 1.0, 0.0], [0.0, 0.0, -1.0])
+        for j, (n, m) in enumerate(Z.indices(kind, 37)):
+            norm = Z.norm_constant(kind, n, m)
+            assert A[0, j] == (0.0 if m != 0 else norm * (-1) ** (n // 2))
+            assert A[1, j] == pytest.approx(norm if m >= 0 else 0.0, abs=1e-13)
+
+
+@pytest.mark.parametrize("case", M.names(GOLD, "smtf_cases"))
+def test_host_sampled_mtf_reproduces_the_reference(case):
+    g = GOLD
+    got = M.numpy_sampled_mtf(g[f"{case}/coeffs"], str(g[f"{case}/kind"]), g[f"{case}/x"],
+                              g[f"{case}/y"], g[f"{case}/opd"], g[f"{case}/intensity"],
+                              g[f"{case}/shifts"])
+    assert float(np.abs(got - g[f"{case}/mtf"]).max()) <= M.smtf_bound(g[f"{case}/spread"],
+                                                                       g[f"{case}/x"].size)
+
+
+# ------------------------------------------------------------------ stand-alone host logic
+@pytest.fixture
+def cpu_engine(monkeypatch):
+    from tests._fake_engine import OracleEngine
+    monkeypatch.setattr(tr, "_make_engine", lambda table, device: OracleEngine(table, device))
+
+
+def _numpy_fit(x, y, z, kind="fringe", num_terms=37, intensity=None, *, device=None):
+    c, _ = M.numpy_fit(*(torch.as_tensor(v).numpy() for v in (x, y, z)), kind, num_terms,
+                       None if intensity is None else torch.as_tensor(intensity).numpy())
+    return torch.as_tensor(c), torch.zeros(1, dtype=torch.int32)
+
+
+def _numpy_smtf(coeffs, kind, x, y, opd, intensity, shifts, *, device=None, **kw):
+    return torch.as_tensor(M.numpy_sampled_mtf(*(torch.as_tensor(v).numpy() for v in (coeffs,)),
+                                               kind, *(torch.as_tensor(v).numpy()
+                                                       for v in (x, y, opd, intensity)), shifts))
+
+
+def test_paraxial_exit_pupil_and_shifts():
+    for case, lens in (("cooke_n32", "cooke"), ("dgauss_n32", "dgauss")):
+        xpd, xpl = mtf_mod.paraxial_exit_pupil(load_system(M.SYSTEMS[lens]))
+        assert xpd == pytest.approx(float(GOLD[f"{case}/xpd"]), rel=1e-12)
+        assert -xpl == pytest.approx(float(GOLD[f"{case}/xpl"]), rel=1e-12)
+    g, case = GOLD, "cooke_fringe"
+    sh = mtf_mod.pupil_shifts([(0.0, 10.0), (5.0, 0.0)], 0.55, 10.0, -50.0)
+    assert sh.shape == (2, 2) and sh[0, 0] == 0.0 and sh[1, 1] == 0.0
+    assert sh[0, 1] == -50.0 * (0.55 * 1e-3 * 10.0) / (10.0 / 2)
+
+
+@pytest.mark.parametrize("case", M.names(GOLD, "e2e_cases"))
+def test_standalone_sampled_mtf_host_logic(case, cpu_engine, monkeypatch):
+    monkeypatch.setattr(engine, "zernike_fit", _numpy_fit)
+    monkeypatch.setattr(engine, "sampled_mtf", _numpy_smtf)
+    tracer = tr.HipRayTracer(load_system(M.SYSTEMS[str(GOLD[f"{case}/system"])]), "cpu",
+                             dtype=torch.float64)
+    m = SampledMTF(tracer, tuple(GOLD[f"{case}/field"]), float(GOLD[f"{case}/wavelength"]),
+                   num_rays=int(GOLD[f"{case}/num_rays"]))
+    assert m.zernike_coeffs.shape == (37,)
+    got = m.calculate_mtf([tuple(f) for f in GOLD[f"{case}/freqs"]])
+    want = GOLD[f"{case}/mtf"]
+    assert isinstance(got, list) and len(got) == want.size
+    err = float(np.abs(np.array([float(v) for v in got]) - want).max())
+    assert err <= 3 * float(GOLD[f"{case}/spread"]), (case, err)
+    assert m.calculate_mtf([]) == []
+    m.xpd = 0.0        # sampled.py:163-168
+    assert m.calculate_mtf([(0.0, 0.0), (0.0, 3.0)]) == [1.0, 0.0]
+
+
+def test_standalone_zernike_opd_host_logic(cpu_engine, monkeypatch):
+    monkeypatch.setattr(engine, "zernike_fit", _numpy_fit)
+    tracer = tr.HipRayTracer(load_system("cooke_generic"), "cpu", dtype=torch.float64)
+    w = float(GOLD["cooke_n32/wavelength"])
+    z = ZernikeOPD(tracer, (0.0, 0.7), w, num_rings=6, zernike_type="standard", num_terms=37)
+    want = GOLD["hex6_standard_37/coeffs"]
+    assert z.num_pts == 127 and z.indices == Z.indices("standard", 37)
+    # the reference's coefficients of the reference's map: trace parity times cond_2(A)
+    assert float(np.abs(z.coeffs.numpy() - want).max()) <= 1e-8
+    with pytest.raises(ValueError, match="ZK_MAX_TERMS"):
+        ZernikeOPD(tracer, (0.0, 0.7), w, num_terms=_capi.ZK_MAX_TERMS + 1)
+    monkeypatch.setattr(engine, "zernike_fit", lambda *a, **k: (
+        torch.full((37,), float("nan")), torch.tensor([_capi.ZK_RANK_DEFICIENT])))
+    with pytest.raises(ValueError, match="rank deficient"):
+        ZernikeOPD(tracer, (0.0, 0.7), w, num_rings=6)
+
+
+def test_standalone_zernike_fit_class(monkeypatch):
+    monkeypatch.setattr(engine, "zernike_fit", _numpy_fit)
+    x, y, z, kind, k = M.fit_inputs(GOLD, "hex6_noll_37")
+    f = Z.ZernikeFit(x, y, z, kind, k)
+    assert f.num_pts == 127 and f.indices == Z.indices(kind, k) and f.status == 0
+    assert float(np.abs(f.coeffs.numpy() - GOLD["hex6_noll_37/coeffs"]).max()) <= 1e-13
+    assert "fewer valid points" in Z.status_text(_capi.ZK_TOO_FEW)
+    assert "non-finite" in Z.status_text(_capi.ZK_NONFINITE | _capi.ZK_RANK_DEFICIENT)
+
+
+# ------------------------------------------------------------------ the seams
+class _Backend(types.ModuleType):
+    _backends = {}
+    name = "torch"
+
+    @classmethod
+    def get_backend(cls):
+        return cls.name
+
+
+@pytest.fixture
+def stand_ins(monkeypatch):
+    from optiland_amd import analysis_seams as seams
+
+    oz = types.ModuleType("optiland.zernike")
+    for name in ("ZernikeFringe", "ZernikeStandard", "ZernikeNoll"):
+        setattr(oz, name, type(name, (), {"__init__": lambda s, c: setattr(s, "coeffs", c)}))
+    fit_mod = types.ModuleType("optiland.zernike.fit")
+    mtf_mod_ = types.ModuleType("optiland.mtf.sampled")
+
+    class ZernikeFit:
+        def _fit(self):
+            self.zernike.coeffs = "reference"
+
+    class SampledMTF:
+        def calculate_mtf(self, frequencies):
+            return ["reference"] * len(frequencies)
+
+    fit_mod.ZernikeFit, mtf_mod_.SampledMTF = ZernikeFit, SampledMTF
+    be = _Backend("be")
+    for k, v in {"optiland": types.ModuleType("optiland"), "optiland.backend": be,
+                 "optiland.zernike": oz, "optiland.zernike.fit": fit_mod,
+                 "optiland.mtf": types.ModuleType("optiland.mtf"),
+                 "optiland.mtf.sampled": mtf_mod_}.items():
+        monkeypatch.setitem(sys.modules, k, v)
+    monkeypatch.setattr(seams, "_ORIG", {})
+    monkeypatch.setattr(seams, "SKIPPED", {})
+    monkeypatch.setattr(seams, "_SEAMS", {k: v for k, v in seams._SEAMS.items()
+                                          if k in ("zfit", "smtf")})
+    monkeypatch.setattr(seams, "STATS", dict(seams.STATS))
+    return seams, be, oz, ZernikeFit, SampledMTF
+
+
+def test_seams_install_fall_back_and_are_removed(stand_ins, monkeypatch, tmp_path):
+    seams, be, oz, ZernikeFit, SampledMTF = stand_ins
+    for key in ("zfit", "zfit_fallback", "smtf", "smtf_fallback"):
+        assert seams.STATS[key] == 0
+    stock = (ZernikeFit.__dict__["_fit"], SampledMTF.__dict__["calculate_mtf"])
+    seams.enable()
+    assert not seams.SKIPPED
+    assert ZernikeFit.__dict__["_fit"] is seams._zernike_fit_fit
+    assert SampledMTF.__dict__["calculate_mtf"] is seams._sampled_mtf_calculate
+    log = tmp_path / "seams.log"
+    monkeypatch.setenv("OPTILAND_HIP_SEAM_LOG", str(log))
+    x = torch.zeros(50, dtype=torch.float64)
+    fit = ZernikeFit()
+    fit.x = fit.y = fit.z = x
+    fit.zernike = oz.ZernikeFringe(torch.ones(10, dtype=torch.float64))
+    mtf = SampledMTF()
+    mtf.zernike_fit, mtf.P1, mtf.intensity, mtf.x_norm, mtf.y_norm = fit, x + 0j, x, x, x
+    mtf.xpd, mtf.xpl, mtf.wavelength = 10.0, -50.0, 0.55
+    # the NumPy backend
+    be.name = "numpy"
+    fit._fit()
+    assert fit.zernike.coeffs == "reference"
+    assert mtf.calculate_mtf([(0.0, 1.0)]) == ["reference"]
+    assert (seams.STATS["zfit_fallback"], seams.STATS["smtf_fallback"]) == (1, 1)
+    assert "zfit: not the torch backend" in log.read_text()
+    assert "smtf: not the torch backend" in log.read_text()
+    # the torch backend with its tensors on the CPU
+    be.name = "torch"
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    fit.zernike.coeffs = torch.ones(10, dtype=torch.float64)
+    fit._fit()
+    assert fit.zernike.coeffs == "reference"
+    fit.zernike.coeffs = torch.ones(10, dtype=torch.float64)
+    assert mtf.calculate_mtf([(0.0, 1.0), (2.0, 0.0)]) == ["reference"] * 2
+    assert (seams.STATS["zfit_fallback"], seams.STATS["smtf_fallback"]) == (2, 2)
+    assert (seams.STATS["zfit"], seams.STATS["smtf"]) == (0, 0)
+    assert log.read_text().count("off the HIP device") == 2
+    seams.disable()
+    assert (ZernikeFit.__dict__["_fit"], SampledMTF.__dict__["calculate_mtf"]) == stock
+
+
+def test_a_seam_whose_target_changed_its_signature_stays_off(stand_ins):
+    seams, _be, _oz, _fit, SampledMTF = stand_ins
+    SampledMTF.calculate_mtf = lambda self, frequencies, normalise=True: []
+    with pytest.warns(RuntimeWarning, match="smtf"):
+        seams.enable()
+    assert "smtf" in seams.SKIPPED and "zfit" in seams._ORIG
+    seams.disable()
+
+
+def test_scalar_pairs():
+    from optiland_amd import analysis_seams as seams
+
+    assert seams._scalar_pairs([(0, 1.5), (torch.tensor(2.0), np.float64(3))]) == \
+        [(0.0, 1.5), (2.0, 3.0)]
+    assert seams._scalar_pairs(torch.tensor([[1.0, 2.0], [3.0, 4.0]])) == [(1.0, 2.0), (3.0, 4.0)]
+    assert seams._scalar_pairs([(torch.zeros(3), 1.0)]) is None
+    assert seams._scalar_pairs([(np.zeros(2), 1.0)]) is None
+    assert seams._scalar_pairs([1.0, 2.0]) is None
+    assert seams._scalar_pairs(torch.zeros(4)) is None

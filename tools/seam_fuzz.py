@@ -11,7 +11,9 @@ HOST build of the kernel source (tests/_hostmath.py).  Families:
   robust ray aiming), sg_trace (the caller's own rays through SurfaceGroup.trace, whole and with
   skip), edit_loop (edit through the updater / trace, six rounds), spot, ee (SpotDiagram,
   EncircledEnergy), opd / opd_centroid / opd_best_fit / opd_detrended (OPD with each reference
-  strategy, tilt removal), fftpsf;
+  strategy, tilt removal), fftpsf, zernike_opd (ZernikeOPD: 37 fringe coefficients), sampled_mtf
+  (SampledMTF at five frequencies; off the HIP device both seams decline and the reference's own
+  fit and loop run on the drop-in's OPD map);
   `others`: RayFan, PupilAberration, Distortion, GridDistortion, FieldCurvature,
   RmsSpotSizeVsField, RmsWavefrontErrorVsField, ThroughFocusSpotDiagram.
 Prints, per family, how many lenses were compared, the worst relative difference (to the largest
@@ -94,6 +96,16 @@ def families(lens, polarised=False, only=None):
 
     def psf():
         return _np(FFTPSF(lens, (0.0, 0.5), w, num_rays=32, grid_size=64).psf)
+
+    def zernike_opd():
+        from optiland.wavefront import ZernikeOPD
+        return _np(ZernikeOPD(lens, (0.0, 0.7), w, num_rings=6).coeffs)
+
+    def sampled_mtf():
+        from optiland.mtf import SampledMTF
+        m = SampledMTF(lens, (0.0, 0.7), w, num_rays=24)
+        return np.array([float(_np(v)) for v in m.calculate_mtf(
+            [(0.0, 0.0), (5.0, 0.0), (0.0, 5.0), (10.0, 10.0), (0.0, 20.0)])])
 
     def edit_loop():
         # an optimiser's pattern: edit the prescription through the reference's updater, trace,
@@ -235,7 +247,7 @@ def families(lens, polarised=False, only=None):
             "edit_loop": edit_loop, "trace_distributions": trace_distributions,
             "trace_generic": trace_generic, "spot": spot, "ee": ee, "opd": opd(), "opd_centroid": opd(strategy="centroid"),
             "opd_best_fit": opd(strategy="best_fit"), "opd_detrended": opd(remove_tilt=True),
-            "fftpsf": psf}
+            "fftpsf": psf, "zernike_opd": zernike_opd, "sampled_mtf": sampled_mtf}
     todo["edit_loop"] = todo.pop("edit_loop")   # last: it edits the lens
     if OTHERS:
         todo = others
