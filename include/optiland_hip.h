@@ -876,7 +876,8 @@ int ol_geometric_mtf(ol_dtype dt, int32_t n_curves, const void* const* coords,
  * refinement with the residual z - A c formed per point.  Five launches; no floating-point
  * atomics, fixed summation order: bit-identical from run to run.  status_out (one int32 on the
  * device) is 0 or an OR of OL_ZK_TOO_FEW (fewer valid points than terms), OL_ZK_RANK_DEFICIENT
- * (a scaled pivot <= 1e-8: rank deficient, or too ill-conditioned for normal equations) and
+ * (a scaled pivot <= 1e-8: rank deficient, or too ill-conditioned for normal equations with one
+ * refinement step -- the test lets cond_2(A) of up to 2.3e6 through and refuses from 3e6) and
  * OL_ZK_NONFINITE (a NaN or an infinity among the valid points); coeffs_out (num_terms doubles)
  * is then NaN.  Stream-ordered workspace (hipMallocAsync).
  *

@@ -6,7 +6,10 @@
 //   field_m = sum_j a_j exp(i k (R_mj - opd_j)) / R_mj * 1/2 (1 + ((P_m - Q_j) . Q_j / Rp) / R_mj)
 //   psf_m   = |field_m|^2,          k = 2 pi / lambda,  R_mj = |P_m - Q_j|
 //
-// fp64 throughout (k R is ~1e6 rad).  Three launches on the caller's stream:
+// fp64 throughout, and beyond it where the phase needs it: k R is ~1e6 rad, so P - Q, |P - Q|^2,
+// R and 1 / lambda are each carried as hi + lo into the phase in cycles (see the loop).  Against
+// the exact field the sum is good to (n_pupil + 32) 2^-52 sum_j |a_j q_mj / R_mj| per pixel
+// (tests/test_gpu_huygens_exact.py).  Three launches on the caller's stream:
 //   1. rays:    one 64-byte record per pupil sample {Q, Q / Rp, a exp(-i k opd)} -- the per-ray
 //               phase is folded into a complex weight once, so a term evaluates ONE sin/cos;
 //   2. partial: lanes own image pixels (kPix per lane, register-blocked), the pupil index is
@@ -49,6 +52,19 @@ static int fail(int code, const char* fmt, ...) {
   vsnprintf(buf, sizeof(buf), fmt, ap);
   va_end(ap);
   return set_last_error(code, buf);
+}
+
+// a + b = s + e and a - b = s + e exactly (Knuth's TwoSum; no operation here may be contracted
+// or reassociated, and none is: contraction only fuses a product into a sum)
+__device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {
+  s = a + b;
+  const double bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
+}
+__device__ __forceinline__ void two_diff(double a, double b, double& s, double& e) {
+  s = a - b;
+  const double bb = s - a;
+  e = (a - (s - bb)) - (b + bb);
 }
 
 // (cos, sin) of 2 pi t, the phase t in cycles: t - rint(t) is exact, so sincospi sees |x| <= 1
@@ -103,9 +119,20 @@ __global__ __launch_bounds__(kBlock) void huygens_partial_kernel(
     const HuygensRay r = rays[j];  // wave-uniform address: scalar loads
 #pragma unroll
     for (int p = 0; p < kPix; ++p) {
-      const double dx = px[p] - r.u, dy = py[p] - r.v, dz = pz[p] - r.w;
-      const double dz2 = dz * dz;
-      const double r2 = fma(dx, dx, fma(dy, dy, dz2));
+      // P - Q as hi + lo: the rounding of the difference alone (half an ulp of 54 mm is
+      // 3.5e-15 mm, 4e-11 rad at 0.55 um) is as much as the rounding of R, see below
+      double dx, dy, dz, dxl, dyl, dzl;
+      two_diff(px[p], r.u, dx, dxl);
+      two_diff(py[p], r.v, dy, dyl);
+      two_diff(pz[p], r.w, dz, dzl);
+      // |P - Q|^2 as r2 + r2l: the three squares and their two sums, each with its exact
+      // rounding error, and the cross terms of the low parts
+      const double sx = dx * dx, sy = dy * dy, sz = dz * dz;
+      double r2, e1, e2;
+      two_sum(sz, sy, r2, e1);
+      two_sum(r2, sx, r2, e2);
+      double r2l = fma(dx, dx, -sx) + fma(dy, dy, -sy) + fma(dz, dz, -sz) + (e1 + e2);
+      r2l = fma(2.0 * dx, dxl, fma(2.0 * dy, dyl, fma(2.0 * dz, dzl, r2l)));
       // R and 1/R from one hardware reciprocal square root: a Goldschmidt step and a Newton
       // correction of R ...
       const double y0 = __builtin_amdgcn_rsq(r2);
@@ -114,12 +141,10 @@ __global__ __launch_bounds__(kBlock) void huygens_partial_kernel(
       g = fma(g, e, g);
       h = fma(h, e, h);
       const double R = fma(fma(-g, g, r2), h, g);
-      // ... then the part of R a double cannot hold: the residual dx^2 + dy^2 + dz^2 - R^2,
-      // formed with fma from the exact square dz^2 (the largest on a pupil seen from its focus)
-      // down, over 2R.  The phase needs it: R / lambda ~ 1e5 cycles, half an ulp of R is
-      // 4e-11 rad -- as much as the reference's own rounding of k R.
-      double d = fma(-R, R, dz2) + fma(dz, dz, -dz2);
-      d = fma(dx, dx, fma(dy, dy, d));
+      // ... then the part of R a double cannot hold: the residual |P - Q|^2 - R^2 (one fma: R^2
+      // is within a few ulp of r2, so the difference rounds 2^-100 r2 down) over 2R.  It matters:
+      // R / lambda ~ 1e5 cycles, half an ulp of R is 4e-11 rad.
+      const double d = fma(-R, R, r2) + r2l;
       const double inv = h + h;
       // t = R / lambda in cycles as t + t_lo: R (R_hi + R_lo) times 1/lambda (hi + lo)
       const double t = R * inv_wl;

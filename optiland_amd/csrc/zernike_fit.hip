@@ -25,14 +25,21 @@
 //   3. solve:  one block: Jacobi scaling S = D G D with D = diag(G)^-1/2, Cholesky S = L L^T,
 //              two triangular solves.  L and D are kept.
 //   4. gram<residual>: A^T (z - A c), the residual formed per point in fp64.
-//   5. refine: the same factor solves for the correction, which is added.  (Plain normal
-//              equations square the condition number; one step of refinement brings the
-//              coefficients back to the accuracy of a backward-stable least-squares solver for
-//              the condition numbers the pivot test lets through.)
+//   5. refine: the same factor solves for the correction, which is added.
+// Plain normal equations square the condition number: the first solution is off by about
+// cond(S) 2^-53 max|c|, and the refinement step with the fp64 residual multiplies that by about
+// cond(S) 2^-53 again, towards the floor cond_2(A) 2^-53 max|c| of a backward-stable
+// least-squares solver.  What has to be small for that is cond(S), and the pivot test does not
+// bound it: the smallest pivot of the factorisation is only an UPPER bound of the smallest
+// eigenvalue of S.  Against exact coefficients (tests/test_gpu_zernike_conditioning.py, the
+// figures in profiles/zernike_fit.txt) the one step keeps the perturbation bound
+// cond_2(A) K 2^-52 max|c| with a margin of 460 x or more up to cond_2(A) = 3e5; fits whose
+// smallest pivot is 1.5e-8 ... 7e-8, just above the test, have cond_2(A) = 1e6 ... 2.3e6 (cond(S)
+// of a few 1e12) and keep it by 23 x down to 1.2 x (1.04e-8 against 1.27e-8 at a pivot of 1.5e-8).
+// That is where the test has to stand for ONE step; a second one would leave 1e-11 there.
 // The status word: fewer valid points than terms; a scaled pivot <= kZkPivotMin (rank
-// deficient, or too ill-conditioned for one refinement step: cond(S) >~ 1e8 leaves
-// (cond(S) 2^-53)^2 ~ 1e-16 after it, anything beyond that belongs to an SVD); a non-finite
-// input.  With a status the coefficients are NaN.
+// deficient, or too ill-conditioned for one refinement step -- see above; such a problem
+// belongs to an SVD); a non-finite input.  With a status the coefficients are NaN.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -337,6 +344,15 @@ __global__ __launch_bounds__(kZkBlock) void zk_eval_kernel(ZkTable tb,
     out[i] = zk_sum(tb, coeffs, x[i], y[i]);
 }
 
+// the reference's mask `sqrt(xs**2 + ys**2) > 1.0`, every operation rounded as NumPy rounds it:
+// with the sum of squares contracted into an fma, points within two ulp of the rim land on the
+// other side, and each of them moves the MTF by 1 / n
+__device__ __forceinline__ bool smtf_outside(double xs, double ys) {
+#pragma clang fp contract(off)
+  const double xx = xs * xs, yy = ys * ys;
+  return sqrt(xx + yy) > 1.0;
+}
+
 // grid = (point chunks, frequencies); partial[f][chunk] = (re, im, sum of the intensity)
 __global__ __launch_bounds__(kZkBlock) void smtf_kernel(
     ZkTable tb, const double* __restrict__ coeffs, int64_t n, const double* __restrict__ x,
@@ -352,7 +368,7 @@ __global__ __launch_bounds__(kZkBlock) void smtf_kernel(
     const double w = intensity[i];
     total += w;
     const double xs = x[i] - dx, ys = y[i] - dy;
-    if (sqrt(xs * xs + ys * ys) > 1.0) continue;  // sampled.py:190-193 (a NaN stays in)
+    if (smtf_outside(xs, ys)) continue;  // sampled.py:190-193 (a NaN stays in)
     const double amp = sqrt(w);
     // the phase in cycles; t - rint(t) is exact, so sincospi sees |argument| <= 1
     const double t = (p1 ? 0.0 : opd[i]) - zk_sum(tb, coeffs, xs, ys);

@@ -1,0 +1,105 @@
+"""The exact fixtures (tests/golden/exact_*.npz) and their generator, tools/make_golden_exact.py,
+checked on the host: the loaders and bounds of tests/_exact.py without mpmath, and with it one
+case of every fixture made again bit for bit, the mpmath basis against `basis_numpy` and the
+mpmath Huygens field against `direct_field`."""
+
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+from optiland_amd import zernike as Z
+from tests import _exact as E
+from tests import _huygens as H
+from tests import _zernike_fit as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def gen():
+    pytest.importorskip("mpmath")
+    spec = importlib.util.spec_from_file_location(
+        "make_golden_exact", os.path.join(ROOT, "tools", "make_golden_exact.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _same(made, stored, prefix):
+    keys = [k for k in made if k.startswith(prefix)]
+    assert keys
+    for k in keys:
+        a, b = np.asarray(made[k]), stored[k]
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k
+
+
+def test_fixtures_hold_what_the_gpu_tests_read():
+    z, h, s = E.load("zernike"), E.load("huygens"), E.load("smtf")
+    for case in E.names(z, "ladder") + E.names(z, "window") + E.names(z, "masked"):
+        x, y, zz, kind, k, inten = E.fit_inputs(z, case)
+        assert x.shape == y.shape == zz.shape == (300,) and z[f"{case}/coeffs"].shape == (k,)
+        assert (inten is not None) == case.endswith("_masked")
+        # the stored condition number is that of the host's design matrix too
+        lit = slice(None) if inten is None else inten > 0
+        cond = np.linalg.cond(Z.basis_numpy(kind, k, x[lit], y[lit]))
+        assert cond == pytest.approx(float(z[f"{case}/cond"]), rel=1e-6)
+    # the ladder stays clear of the pivot test, the window crosses it
+    assert min(float(z[f"{c}/min_pivot"]) for c in E.names(z, "ladder")) > 1e-7
+    pivots = [float(z[f"{c}/min_pivot"]) for c in E.names(z, "window")]
+    assert max(pivots) > 1e-8 > min(pivots)
+    for kind in E.names(z, "kinds"):
+        assert z[f"eval/{kind}/basis"].shape == (z[f"eval/{kind}/x"].size, 120)
+    for case in E.names(h, "cases"):
+        n = h[f"{case}/pupil_x"].size
+        assert n <= 300 and h[f"{case}/image_x"].size <= 8
+        assert (h[f"{case}/numpy_err"] / E.huygens_bound(n, h[f"{case}/scale"])).max() > 1.0
+    assert {"waves0.3", "waves30", "waves300"} <= set(E.names(s, "cases"))
+    assert s["x"].size == 257 and s["shifts"].shape == (5, 2) and int(s["rim/fused_flips"]) > 0
+    for name in ("zernike", "huygens", "smtf"):
+        assert os.path.getsize(os.path.join(E.GOLDEN, f"exact_{name}.npz")) < 1 << 20
+
+
+def test_one_case_of_every_fixture_is_made_again_bit_for_bit(gen):
+    _same(gen.make_zernike(only="fit/fringe37_rho0.43"), E.load("zernike"), "fit/fringe37_rho0.43/")
+    _same(gen.make_huygens(only="lambda_193nm"), E.load("huygens"), "lambda_193nm/")
+    _same(gen.make_smtf(only="waves300"), E.load("smtf"), "waves300/")
+
+
+@pytest.mark.parametrize("kind", Z.KINDS)
+def test_mpmath_basis_agrees_with_the_host_basis(gen, kind):
+    """Two Horner-free / Horner evaluations apart: the `abs_basis` bound of the eval test,
+    (2 (2 s + 2) + K) 2^-52 norm sum_k |c_k| r^(n - 2k), halved because one side is exact."""
+    rng = np.random.default_rng(5)
+    r, th = np.sqrt(rng.random(12)), 2 * np.pi * rng.random(12)
+    x = np.concatenate([r * np.cos(th), [0.0, 1.0, 0.0, 0.6, 1.2, 1e-8]])
+    y = np.concatenate([r * np.sin(th), [0.0, 0.0, -1.0, 0.8, 0.0, 0.0]])
+    exact = np.array([[float(v) for v in row] for row in gen.mp_basis(kind, 120, x, y)])
+    host = Z.basis_numpy(kind, 120, x, y)
+    scale = M.abs_basis(kind, 120, x, y)
+    err = np.abs(host - exact)
+    print(f"\n[basis] {kind}: max |host - mpmath| / |Z| = "
+          f"{float((err[scale > 0] / scale[scale > 0]).max()):.3e} (bound {E.eval_limit(120):.3e})")
+    assert np.all(err <= E.eval_limit(120) * scale)
+    # ... and the stored matrix is this function's
+    g = E.load("zernike")
+    again = gen.mp_basis(kind, 120, g[f"eval/{kind}/x"][:4], g[f"eval/{kind}/y"][:4])
+    assert np.array_equal(np.array([[float(v) for v in row] for row in again]),
+                          g[f"eval/{kind}/basis"][:4])
+
+
+def test_mpmath_huygens_field_agrees_with_the_direct_sum(gen):
+    g = E.load("huygens")
+    for case in E.names(g, "cases"):
+        args = tuple(g[f"{case}/{a}"] for a in H.ARGS)
+        err = np.abs(H.direct_field(*args) - g[f"{case}/field"])
+        # the same NumPy on the same inputs: the stored error (another libm's exp may move its
+        # last bits), which is small against the field: k R 2^-53 ~ 1e-10 rad per term
+        assert err.max() <= 2 * g[f"{case}/numpy_err"].max(), case
+        assert np.all(err <= 1e-9 * g[f"{case}/scale"]), case
+    args = gen.huygens_args("golden")
+    few = tuple(np.asarray(a)[:2] for a in args[:3]) + args[3:]
+    field, scale = gen.mp_huygens(*few)
+    assert np.array_equal(field, g["golden/field"][:2])
+    assert np.array_equal(scale, g["golden/scale"][:2])
