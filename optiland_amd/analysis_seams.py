@@ -1161,6 +1161,56 @@ def _uniform_generate_points(self, num_points):
     return None
 
 
+# --------------------------------------------------------------------------- fp64 analysis kernels
+# (Huygens PSF, geometric MTF, Zernike fit, sampled MTF: what their four seams share)
+def _grad_mode(be) -> bool:
+    try:
+        return bool(be._backends[be.get_backend()]._config.grad_mode.requires_grad)
+    except Exception:  # noqa: BLE001 - a backend without that configuration object
+        return False
+
+
+def _torch_on_hip(seam, be) -> bool:
+    if be.get_backend() != "torch" or not torch.cuda.is_available():
+        _why(seam, "not the torch backend on a HIP device")
+        return False
+    return True
+
+
+def _device_ready(seam, tensors, has, entry) -> bool:
+    """Whether the call can be served: every tensor on the HIP device, no autograd, a library
+    in which `has` (a `_capi.has_*`) finds `entry`."""
+    import optiland.backend as be
+
+    from . import _capi
+
+    if any(not isinstance(t, torch.Tensor) or t.device.type != "cuda" for t in tensors):
+        _why(seam, "an input lives off the HIP device")
+        return False
+    if _grad_mode(be) or any(t.requires_grad for t in tensors):
+        _why(seam, "autograd")
+        return False
+    try:
+        lib = _capi.load()
+    except _capi.HipExtensionError as exc:
+        _why(seam, str(exc))
+        return False
+    if not has(lib):
+        _why(seam, f"library without {entry}")
+        return False
+    return True
+
+
+def _served(key, out, self, *args):
+    """Count the call in STATS: `out`, what the device function gave, or -- for None -- what
+    the reference's own method gives."""
+    if out is None:
+        STATS[key + "_fallback"] += 1
+        return _ORIG[key](self, *args)
+    STATS[key] += 1
+    return out
+
+
 # --------------------------------------------------------------------------- Huygens PSF
 _HUYGENS_ARGS = ("image_x", "image_y", "image_z", "pupil_x", "pupil_y", "pupil_z", "pupil_amp",
                  "pupil_opd", "wavelength", "Rp")
@@ -1177,12 +1227,7 @@ def _huygens_torch_compute(self, image_x, image_y, image_z, pupil_x, pupil_y, pu
     autograd, or with a library that lacks the kernel."""
     args = (image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, pupil_amp, pupil_opd,
             wavelength, Rp)
-    out = _huygens_device(self, *args)
-    if out is None:
-        STATS["huygens_fallback"] += 1
-        return _ORIG["huygens"](self, *args)
-    STATS["huygens"] += 1
-    return out
+    return _served("huygens", _huygens_device(self, *args), self, *args)
 
 
 def _huygens_device(self, *args):
@@ -1195,23 +1240,7 @@ def _huygens_device(self, *args):
         _why("huygens", f"summation device {dev} is not a HIP device")
         return None
     tensors = [a for a in args if isinstance(a, torch.Tensor)]
-    try:
-        grad = be._backends[be.get_backend()]._config.grad_mode.requires_grad
-    except Exception:  # noqa: BLE001 - a backend without that configuration object
-        grad = False
-    if grad or any(t.requires_grad for t in tensors):
-        _why("huygens", "autograd")
-        return None
-    if any(t.device.type != "cuda" for t in tensors):
-        _why("huygens", "an input lives off the HIP device")
-        return None
-    try:
-        lib = _capi.load()
-    except _capi.HipExtensionError as exc:
-        _why("huygens", str(exc))
-        return None
-    if not _capi.has_huygens(lib):
-        _why("huygens", "library without ol_huygens_psf")
+    if not _device_ready("huygens", tensors, _capi.has_huygens, "ol_huygens_psf"):
         return None
     from .engine import huygens_sum
 
@@ -1233,12 +1262,7 @@ def _geometric_mtf_generate(self):
     torch backend, whose `torch.histogram(x.float())` bins in float32.  Falls back to the
     reference's method off the HIP device, under autograd, with a library that lacks the kernel,
     and for a non-finite hit (the user then sees the reference's own error)."""
-    out = _geometric_mtf_device(self)
-    if out is None:
-        STATS["geo_mtf_fallback"] += 1
-        return _ORIG["geo_mtf"](self)
-    STATS["geo_mtf"] += 1
-    return out
+    return _served("geo_mtf", _geometric_mtf_device(self), self)
 
 
 def _geometric_mtf_device(self):
@@ -1246,8 +1270,7 @@ def _geometric_mtf_device(self):
 
     from . import _capi
 
-    if be.get_backend() != "torch" or not torch.cuda.is_available():
-        _why("geo_mtf", "not the torch backend on a HIP device")
+    if not _torch_on_hip("geo_mtf", be):
         return None
     try:
         curves = [c for field_data in self.data for c in (field_data[0].y, field_data[0].x)]
@@ -1260,24 +1283,11 @@ def _geometric_mtf_device(self):
                          or not t.is_floating_point() or t.ndim != 1 for t in tensors):
         _why("geo_mtf", "hits or frequencies live off the HIP device")
         return None
-    try:
-        grad = be._backends[be.get_backend()]._config.grad_mode.requires_grad
-    except Exception:  # noqa: BLE001 - a backend without that configuration object
-        grad = False
-    if grad or any(t.requires_grad for t in tensors):
-        _why("geo_mtf", "autograd")
+    if not _device_ready("geo_mtf", tensors, _capi.has_geometric_mtf, "ol_geometric_mtf"):
         return None
     n_bins = int(self.num_points) + 1
     if not 1 <= n_bins <= _capi.MTF_MAX_BINS or freq.numel() < 1:
         _why("geo_mtf", f"{n_bins} bins")
-        return None
-    try:
-        lib = _capi.load()
-    except _capi.HipExtensionError as exc:
-        _why("geo_mtf", str(exc))
-        return None
-    if not _capi.has_geometric_mtf(lib):
-        _why("geo_mtf", "library without ol_geometric_mtf")
         return None
     from .engine import geometric_mtf_launch
 
@@ -1300,13 +1310,6 @@ def _geometric_mtf_device(self):
 
 
 # --------------------------------------------------------------------------- Zernike fit, sampled MTF
-def _grad_mode(be) -> bool:
-    try:
-        return bool(be._backends[be.get_backend()]._config.grad_mode.requires_grad)
-    except Exception:  # noqa: BLE001 - a backend without that configuration object
-        return False
-
-
 def _zernike_kind(zernike):
     """'fringe' / 'standard' / 'noll' for an instance of exactly one of the reference's three
     classes, else None (a subclass may override the basis or `poly`)."""
@@ -1319,31 +1322,6 @@ def _zernike_kind(zernike):
     return None
 
 
-def _zk_ready(seam, be, tensors):
-    """The library when the call can be served: torch backend, every tensor on the HIP device,
-    no autograd, a library with the three entry points."""
-    from . import _capi
-
-    if be.get_backend() != "torch" or not torch.cuda.is_available():
-        _why(seam, "not the torch backend on a HIP device")
-        return None
-    if any(not isinstance(t, torch.Tensor) or t.device.type != "cuda" for t in tensors):
-        _why(seam, "an input lives off the HIP device")
-        return None
-    if _grad_mode(be) or any(t.requires_grad for t in tensors):
-        _why(seam, "autograd")
-        return None
-    try:
-        lib = _capi.load()
-    except _capi.HipExtensionError as exc:
-        _why(seam, str(exc))
-        return None
-    if not _capi.has_zernike_fit(lib):
-        _why(seam, "library without ol_zernike_fit")
-        return None
-    return lib
-
-
 def _zernike_fit_fit(self):
     """zernike/fit.py:101-118 (`ZernikeFit._fit`) with `ol_zernike_fit` on `self.x / y / z`: one
     read-back, the status word.  `self.zernike.coeffs` ends up a device tensor of the backend's
@@ -1351,12 +1329,10 @@ def _zernike_fit_fit(self):
     minimum-norm answer -- off the HIP device, under autograd, for tensors other than fp64, a
     Zernike class that is not one of the reference's three, more than ZK_MAX_TERMS terms, and
     when the status word says rank deficient, too few points or non-finite."""
-    out = _zernike_fit_device(self)
-    if out is None:
-        STATS["zfit_fallback"] += 1
-        return _ORIG["zfit"](self)
-    STATS["zfit"] += 1
-    self.zernike.coeffs = out
+    coeffs = _zernike_fit_device(self)
+    if coeffs is None:
+        return _served("zfit", None, self)
+    self.zernike.coeffs = _served("zfit", coeffs, self)
     return None
 
 
@@ -1366,7 +1342,8 @@ def _zernike_fit_device(self):
     from . import _capi
 
     tensors = [self.x, self.y, self.z]
-    if _zk_ready("zfit", be, tensors) is None:
+    if not (_torch_on_hip("zfit", be)
+            and _device_ready("zfit", tensors, _capi.has_zernike_fit, "ol_zernike_fit")):
         return None
     if any(t.dtype != torch.float64 or t.ndim != 1 for t in tensors):
         _why("zfit", "x / y / z are not one-dimensional fp64 tensors")
@@ -1399,12 +1376,7 @@ def _sampled_mtf_calculate(self, frequencies):
     entry per frequency (0-d device tensors).  Falls back to the reference's method for
     `xpd == 0`, under autograd, off the HIP device, for a Zernike object that is not one of the
     reference's three classes (it may override `poly`), and for non-scalar frequencies."""
-    out = _sampled_mtf_device(self, frequencies)
-    if out is None:
-        STATS["smtf_fallback"] += 1
-        return _ORIG["smtf"](self, frequencies)
-    STATS["smtf"] += 1
-    return out
+    return _served("smtf", _sampled_mtf_device(self, frequencies), self, frequencies)
 
 
 def _scalar_pairs(frequencies):
@@ -1438,7 +1410,8 @@ def _sampled_mtf_device(self, frequencies):
     except AttributeError:
         _why("smtf", "not the attributes of sampled.py")
         return None
-    if _zk_ready("smtf", be, tensors) is None:
+    if not (_torch_on_hip("smtf", be)
+            and _device_ready("smtf", tensors, _capi.has_zernike_fit, "ol_zernike_fit")):
         return None
     if any(isinstance(v, torch.Tensor) and v.requires_grad for v in (self.xpd, self.xpl)):
         _why("smtf", "autograd")
@@ -1465,11 +1438,10 @@ def _sampled_mtf_device(self, frequencies):
         return None
     if not pairs:
         return []
-    # sampled.py:158-178, the reference's operations in its order, in fp64 on the host
-    wl_mm = _f(self.wavelength) * 1e-3
-    shifts = xpl * (wl_mm * np.asarray(pairs, dtype=np.float64)) / (xpd / 2)
     from .engine import sampled_mtf
+    from .mtf import pupil_shifts
 
+    shifts = pupil_shifts(pairs, _f(self.wavelength), xpd, xpl)
     p1 = self.P1.detach()
     mtf = sampled_mtf(coeffs.detach(), kind, self.x_norm.detach(), self.y_norm.detach(), None,
                       self.intensity.detach(), shifts,

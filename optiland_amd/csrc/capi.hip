@@ -23,10 +23,10 @@
 #include "trace_launch.h"
 
 namespace {
-
 thread_local std::string g_err;
+}
 
-int fail(int code, const char* fmt, ...) {
+int ol::failf(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -36,11 +36,15 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+namespace {
+
+using ol::failf;
+
 #define OL_HIP_CHECK(expr)                                                        \
   do {                                                                            \
     hipError_t e_ = (expr);                                                       \
     if (e_ != hipSuccess)                                                         \
-      return fail(OL_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
+      return failf(OL_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
   } while (0)
 
 void mat3_mul_abt(const double* A, const double* B, double* out) {  // A * B^T
@@ -273,8 +277,8 @@ struct ol_system {
 
 #define OL_CHECK_CONSISTENT(sys, who)                                                          \
   if (!(sys)->consistent)                                                                      \
-    return fail(OL_EINVAL, who ": the system's tables are inconsistent after a failed "         \
-                               "ol_system_update (destroy it and create a new one)")
+    return failf(OL_EINVAL, who ": the system's tables are inconsistent after a failed "         \
+                                "ol_system_update (destroy it and create a new one)")
 
 namespace {
 
@@ -437,13 +441,13 @@ int do_trace(const ol_system* sys, const DeviceTable<T>& tab, int64_t n, void* c
   a.n_surf = sys->n_surf;
   if (family == ol::kNrReference) {
     if (!a.nr_iters)
-      return fail(OL_EINVAL, "ol_trace: a surface of the range carries OL_SURF_REFERENCE_NEWTON: "
-                             "pass ol_trace_extras.newton_iterations (see ol_newton_count)");
+      return failf(OL_EINVAL, "ol_trace: a surface of the range carries OL_SURF_REFERENCE_NEWTON: "
+                              "pass ol_trace_extras.newton_iterations (see ol_newton_count)");
     if (a.spot)
-      return fail(OL_EUNSUPPORTED, "ol_trace_ex: no spot epilogue on a reference-Newton range");
+      return failf(OL_EUNSUPPORTED, "ol_trace_ex: no spot epilogue on a reference-Newton range");
   }
   hipError_t e = ol::launch_trace<T>(a, vec, family, stream);
-  if (e != hipSuccess) return fail(OL_EHIP, "trace launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "trace launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -451,9 +455,9 @@ int do_trace(const ol_system* sys, const DeviceTable<T>& tab, int64_t n, void* c
 // Newton iteration count is a property of the batch
 int refuse_reference_newton(const char* who, const ol_system* sys) {
   if (newton_family(sys, 0, sys->n_surf - 1) != ol::kNrReference) return OL_OK;
-  return fail(OL_EUNSUPPORTED, "%s: the system carries OL_SURF_REFERENCE_NEWTON surfaces "
-                               "(reference stop rule): generate with ol_generate_rays, count "
-                               "with ol_newton_count, trace with ol_trace_ex", who);
+  return failf(OL_EUNSUPPORTED, "%s: the system carries OL_SURF_REFERENCE_NEWTON surfaces "
+                                "(reference stop rule): generate with ol_generate_rays, count "
+                                "with ol_newton_count, trace with ol_trace_ex", who);
 }
 
 // ol_raygen_inputs -> working precision; host-side part of the range validation
@@ -461,15 +465,15 @@ int refuse_reference_newton(const char* who, const ol_system* sys) {
 template <typename T>
 int convert_inputs(const char* who, const ol_raygen_inputs* in, uint32_t* status,
                    ol::RaygenIn<T>& o, bool& aligned) {
-  if (!in || !in->px || !in->py) return fail(OL_EINVAL, "%s: NULL argument", who);
+  if (!in || !in->px || !in->py) return failf(OL_EINVAL, "%s: NULL argument", who);
   if ((in->hx == nullptr) != (in->hy == nullptr) || (in->vx == nullptr) != (in->vy == nullptr))
-    return fail(OL_EINVAL, "%s: hx/hy (and vx/vy) must be given together", who);
+    return failf(OL_EINVAL, "%s: hx/hy (and vx/vy) must be given together", who);
   if ((in->flags & (OL_RAYGEN_CHECK_FIELD | OL_RAYGEN_CHECK_PUPIL)) && !status)
-    return fail(OL_EINVAL, "%s: a CHECK flag needs a status word", who);
+    return failf(OL_EINVAL, "%s: a CHECK flag needs a status word", who);
   if ((in->flags & OL_RAYGEN_CHECK_FIELD) && !in->hx) {
     auto bad = [](double v) { return !(v >= -1.0 && v <= 1.0); };
     if (bad(in->hx0) || bad(in->hy0))  // real_ray_tracer.py:156-173, same text
-      return fail(OL_EINVAL, "Normalized field coordinates must be within (-1, 1)");
+      return failf(OL_EINVAL, "Normalized field coordinates must be within (-1, 1)");
   }
   o.hx = static_cast<const T*>(in->hx);
   o.hy = static_cast<const T*>(in->hy);
@@ -504,7 +508,7 @@ int do_generate_rays(const ol_raygen_params* p, int64_t n, const ol_raygen_input
   T* o[8];
   for (int k = 0; k < 8; ++k) o[k] = static_cast<T*>(out[k]);
   hipError_t e = ol::launch_raygen<T>(raygen_dev(p), ri, n, o, status, stream);
-  if (e != hipSuccess) return fail(OL_EHIP, "raygen launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "raygen launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -544,8 +548,8 @@ int do_trace_generate(const ol_system* sys, const DeviceTable<T>& tab, int64_t n
             (prt ? ol::kTracePrtIdentity : 0u) | (rays_out ? ol::kTraceWriteRays : 0u);
   if (extras && extras->updated_intensity && extras->update_intensity_state) {
     if (!prt)
-      return fail(OL_EINVAL, "ol_trace_generate: the update_intensity epilogue needs a "
-                             "polarised launch (prt)");
+      return failf(OL_EINVAL, "ol_trace_generate: the update_intensity epilogue needs a "
+                              "polarised launch (prt)");
     const ol_polarization_state* ps = extras->update_intensity_state;
     ol::PolStateDev st{ps->is_polarized, ps->Ex, ps->Ey, ps->phase_x, ps->phase_y};
     a.pf = ol::PolFields<T>(st);
@@ -565,7 +569,7 @@ int do_trace_generate(const ol_system* sys, const DeviceTable<T>& tab, int64_t n
               reinterpret_cast<uintptr_t>(a.i_updated) % 8 == 0;
   }
   hipError_t e = ol::launch_trace_generate<T>(a, family, pair_ok, stream);
-  if (e != hipSuccess) return fail(OL_EHIP, "trace launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "trace launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -598,7 +602,7 @@ int do_trace_spot(const ol_system* sys, const DeviceTable<T>& tab, int64_t n,
   a.wl = wl;
   a.tiles_per_block = 1;
   hipError_t e = ol::launch_spot_trace<T>(a, vec, newton_family(sys, 0, sys->n_surf - 1), stream);
-  if (e != hipSuccess) return fail(OL_EHIP, "spot launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "spot launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -655,7 +659,7 @@ int do_trace_spot_batch(const ol_system* sys, const DeviceTable<T>& tab, int64_t
     b.c[c].n_wl = from->n_wl;
   }
   hipError_t e = ol::launch_spot_batch<T>(a, b, vec, newton_family(sys, 0, sys->n_surf - 1), stream);
-  if (e != hipSuccess) return fail(OL_EHIP, "spot batch launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "spot batch launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -689,7 +693,7 @@ int do_wavefront_reference(const ol_system* sys, const DeviceTable<T>& tab,
   a.wl = wl;
   hipError_t e = ol::launch_chief_reference<T>(a, newton_family(sys, 0, sys->n_surf - 1), stream);
   if (e != hipSuccess)
-    return fail(OL_EHIP, "chief-ray launch failed: %s", hipGetErrorString(e));
+    return failf(OL_EHIP, "chief-ray launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -704,8 +708,8 @@ int do_trace_opd(const ol_system* sys, const DeviceTable<T>& tab, int64_t n,
   bool vec = true;
   if (int rc = convert_inputs<T>("ol_trace_opd", in, status, a.in, vec)) return rc;
   if (a.in.hx != nullptr || a.in.vx != nullptr)
-    return fail(OL_EINVAL, "ol_trace_opd: one field point per launch (launch-uniform field and "
-                           "vignetting, no hx / hy / vx / vy planes)");
+    return failf(OL_EINVAL, "ol_trace_opd: one field point per launch (launch-uniform field and "
+                            "vignetting, no hx / hy / vx / vy planes)");
   if (n == 0) return OL_OK;
   a.surf = tab.surf;
   a.cold = tab.cold;
@@ -732,13 +736,11 @@ int do_trace_opd(const ol_system* sys, const DeviceTable<T>& tab, int64_t n,
   for (int k = 0; k < 3; ++k) vec = vec && aligned16(a.pupil[k]);
   hipError_t e =
       ol::launch_opd_trace<T>(a, vec, newton_family(sys, 0, sys->n_surf - 1), stream);
-  if (e != hipSuccess) return fail(OL_EHIP, "opd launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "opd launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
 }  // namespace
-
-int ol::set_last_error(int code, const char* message) { return fail(code, "%s", message); }
 
 extern "C" {
 
@@ -749,8 +751,8 @@ int ol_set_tuning(int32_t knob, int32_t value) {
   switch (knob) {
     case OL_TUNE_RAYS_PER_THREAD:
       if (value < 0 || value > 3)
-        return fail(OL_EINVAL, "ol_set_tuning: rays per thread must be 0 (auto), 1, 2 (vector) "
-                               "or 3 (fp32 pair)");
+        return failf(OL_EINVAL, "ol_set_tuning: rays per thread must be 0 (auto), 1, 2 (vector) "
+                                "or 3 (fp32 pair)");
       ol::tuning().rays_per_thread = value;
       return OL_OK;
     case OL_TUNE_COMPACT:
@@ -758,17 +760,17 @@ int ol_set_tuning(int32_t knob, int32_t value) {
       return OL_OK;
     case OL_TUNE_RECORD_WG_CAP:
       if (value < 0 || value > 8)
-        return fail(OL_EINVAL, "ol_set_tuning: record workgroup cap 0 (default policy), "
-                               "1 (never) or 2 ... 8");
+        return failf(OL_EINVAL, "ol_set_tuning: record workgroup cap 0 (default policy), "
+                                "1 (never) or 2 ... 8");
       ol::tuning().record_wg_cap = value;
       return OL_OK;
     case OL_TUNE_FIT_GRID:
       if (value < 0 || value > ol::kFitMaxBlocks)
-        return fail(OL_EINVAL, "ol_set_tuning: fit grid 0 (default) ... %d", ol::kFitMaxBlocks);
+        return failf(OL_EINVAL, "ol_set_tuning: fit grid 0 (default) ... %d", ol::kFitMaxBlocks);
       ol::tuning().fit_grid = value;
       return OL_OK;
     default:
-      return fail(OL_EINVAL, "ol_set_tuning: unknown knob %d", knob);
+      return failf(OL_EINVAL, "ol_set_tuning: unknown knob %d", knob);
   }
 }
 
@@ -777,10 +779,10 @@ namespace {
 int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
                  const double* coeffs, int32_t n_coeffs, const ol_surface_optics* optics,
                  int32_t n_wavelengths, Staged& st) {
-  if (!surf || n_surf <= 0) return fail(OL_EINVAL, "%s: no surfaces", who);
-  if (!optics || n_wavelengths <= 0) return fail(OL_EINVAL, "%s: no optics table", who);
+  if (!surf || n_surf <= 0) return failf(OL_EINVAL, "%s: no surfaces", who);
+  if (!optics || n_wavelengths <= 0) return failf(OL_EINVAL, "%s: no optics table", who);
   if (n_coeffs < 0 || (n_coeffs > 0 && !coeffs))
-    return fail(OL_EINVAL, "%s: bad coefficient buffer", who);
+    return failf(OL_EINVAL, "%s: bad coefficient buffer", who);
 
   st.surf.assign(n_surf, HostSurf());
   std::vector<HostSurf>& dev = st.surf;
@@ -792,19 +794,19 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     HostSurf& d = dev[i];
     std::memset(&d, 0, sizeof(d));
     if (s.geom_kind < OL_GEOM_PLANE || s.geom_kind > OL_GEOM_TOROIDAL)
-      return fail(OL_EUNSUPPORTED, "surface %d: geometry kind %d", i, s.geom_kind);
+      return failf(OL_EUNSUPPORTED, "surface %d: geometry kind %d", i, s.geom_kind);
     if (s.interaction < OL_INTERACT_RECORD_ONLY || s.interaction > OL_INTERACT_REFLECT)
-      return fail(OL_EUNSUPPORTED, "surface %d: interaction %d", i, s.interaction);
+      return failf(OL_EUNSUPPORTED, "surface %d: interaction %d", i, s.interaction);
     if (s.aperture_kind < OL_AP_NONE || s.aperture_kind > OL_AP_POLYGON)
-      return fail(OL_EUNSUPPORTED, "surface %d: aperture kind %d", i, s.aperture_kind);
+      return failf(OL_EUNSUPPORTED, "surface %d: aperture kind %d", i, s.aperture_kind);
     if (s.coating_kind < OL_COAT_NONE || s.coating_kind > OL_COAT_RETARDER)
-      return fail(OL_EUNSUPPORTED, "surface %d: coating kind %d", i, s.coating_kind);
+      return failf(OL_EUNSUPPORTED, "surface %d: coating kind %d", i, s.coating_kind);
     if (s.n_coeff < 0 || s.coeff_offset < 0)
-      return fail(OL_EINVAL, "surface %d: negative coefficient range", i);
+      return failf(OL_EINVAL, "surface %d: negative coefficient range", i);
     const int per = s.geom_kind == OL_GEOM_ZERNIKE ? 4 : 1;
     const int extra = s.geom_kind == OL_GEOM_CHEBYSHEV ? 2 : 0;
     if ((int64_t)s.coeff_offset + (int64_t)s.n_coeff * per + extra > n_coeffs)
-      return fail(OL_EINVAL, "surface %d: coefficient block exceeds the buffer", i);
+      return failf(OL_EINVAL, "surface %d: coefficient block exceeds the buffer", i);
 
     d.geom = s.geom_kind;
     d.interaction = s.interaction;
@@ -850,7 +852,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     auto stage_polygon = [&](const double* a, double* q) -> int {
       const int64_t voff = (int64_t)a[0], nv = (int64_t)a[1];
       if (voff < 0 || nv < 1 || voff + 2 * nv > n_coeffs)
-        return fail(OL_EINVAL, "surface %d: polygon vertex block outside the buffer", i);
+        return failf(OL_EINVAL, "surface %d: polygon vertex block outside the buffer", i);
       q[0] = (double)dcoef.size();
       q[1] = (double)nv;
       q[2] = q[3] = 0.0;
@@ -860,7 +862,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     if (s.aperture_kind == OL_AP_COMPOSITE) {
       const int64_t off = (int64_t)s.aperture[0], cnt = (int64_t)s.aperture[1];
       if (off < 0 || cnt <= 0 || off + cnt * OL_AP_TOKEN_DOUBLES > n_coeffs)
-        return fail(OL_EINVAL, "surface %d: aperture token list outside the buffer", i);
+        return failf(OL_EINVAL, "surface %d: aperture token list outside the buffer", i);
       // pass 1: converted tokens (polygon vertices are appended to dcoef as they come)
       std::vector<double> toks;
       int depth = 0;
@@ -871,21 +873,21 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
         if (op >= OL_AP_RADIAL && op <= OL_AP_ELLIPTICAL) {
           convert_aperture(op, tok + 1, q);
           if (++depth > OL_AP_MAX_DEPTH)
-            return fail(OL_EUNSUPPORTED, "surface %d: aperture tree too deep", i);
+            return failf(OL_EUNSUPPORTED, "surface %d: aperture tree too deep", i);
         } else if (op == OL_AP_POLYGON) {
           if (int rc = stage_polygon(tok + 1, q)) return rc;
           if (++depth > OL_AP_MAX_DEPTH)
-            return fail(OL_EUNSUPPORTED, "surface %d: aperture tree too deep", i);
+            return failf(OL_EUNSUPPORTED, "surface %d: aperture tree too deep", i);
         } else if (op >= OL_AP_OP_UNION && op <= OL_AP_OP_DIFFERENCE) {
           q[0] = q[1] = q[2] = q[3] = 0.0;
-          if (--depth < 1) return fail(OL_EINVAL, "surface %d: malformed aperture tokens", i);
+          if (--depth < 1) return failf(OL_EINVAL, "surface %d: malformed aperture tokens", i);
         } else {
-          return fail(OL_EUNSUPPORTED, "surface %d: aperture token op %d", i, op);
+          return failf(OL_EUNSUPPORTED, "surface %d: aperture token op %d", i, op);
         }
         toks.push_back((double)op);
         toks.insert(toks.end(), q, q + 4);
       }
-      if (depth != 1) return fail(OL_EINVAL, "surface %d: malformed aperture tokens", i);
+      if (depth != 1) return failf(OL_EINVAL, "surface %d: malformed aperture tokens", i);
       // pass 2: the token list itself, contiguous
       d.ap_off = (int32_t)dcoef.size();
       d.ap_len = (int32_t)cnt;
@@ -901,7 +903,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
       const int need = s.coating_kind == OL_COAT_RETARDER ? 4 : 3;
       const int64_t off = (int64_t)s.coat[0];
       if (off < 0 || off + need > n_coeffs)
-        return fail(OL_EINVAL, "surface %d: coating axis block outside the buffer", i);
+        return failf(OL_EINVAL, "surface %d: coating axis block outside the buffer", i);
       for (int k = 0; k < 3; ++k) d.axis[k] = coeffs[off + k];
       if (s.coating_kind == OL_COAT_RETARDER) {
         d.ret_cos = std::cos(coeffs[off + 3] / 2);
@@ -919,35 +921,35 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
         d.n_coeff = ng;
       } else {
         if (build_zernike_block(src, s.n_coeff, dcoef, int_slots, &ng) != 0)
-          return fail(OL_EINVAL, "surface %d: invalid Zernike (n, m) index", i);
+          return failf(OL_EINVAL, "surface %d: invalid Zernike (n, m) index", i);
         d.n_coeff = ng;
       }
     } else if (s.geom_kind == OL_GEOM_EVEN_ASPHERE || s.geom_kind == OL_GEOM_ODD_ASPHERE ||
                s.geom_kind == OL_GEOM_POLYNOMIAL) {
       if (s.geom_kind == OL_GEOM_POLYNOMIAL &&
           (s.poly_cols <= 0 || s.n_coeff % s.poly_cols != 0))
-        return fail(OL_EINVAL, "surface %d: polynomial grid %d x ? cols %d", i, s.n_coeff,
-                    s.poly_cols);
+        return failf(OL_EINVAL, "surface %d: polynomial grid %d x ? cols %d", i, s.n_coeff,
+                     s.poly_cols);
       d.n_coeff = s.n_coeff;
       dcoef.insert(dcoef.end(), src, src + s.n_coeff);
     } else if (s.geom_kind == OL_GEOM_CHEBYSHEV) {
       if (s.poly_cols <= 0 || s.n_coeff % s.poly_cols != 0)
-        return fail(OL_EINVAL, "surface %d: chebyshev grid %d, cols %d", i, s.n_coeff,
-                    s.poly_cols);
+        return failf(OL_EINVAL, "surface %d: chebyshev grid %d, cols %d", i, s.n_coeff,
+                     s.poly_cols);
       d.n_coeff = s.n_coeff;
       dcoef.push_back(1.0 / src[0]);
       dcoef.push_back(1.0 / src[1]);
       dcoef.insert(dcoef.end(), src + 2, src + 2 + s.n_coeff);
     } else if (s.geom_kind == OL_GEOM_BICONIC) {
       // biconic.py:57-66: cx/cy = 0 for infinite or zero radii
-      if (s.n_coeff != 2) return fail(OL_EINVAL, "surface %d: biconic needs {Ry, ky}", i);
+      if (s.n_coeff != 2) return failf(OL_EINVAL, "surface %d: biconic needs {Ry, ky}", i);
       const double Rx = s.radius, Ry = src[0];
       d.cv = (std::isinf(Rx) || Rx == 0.0) ? 0.0 : 1.0 / Rx;
       d.n_coeff = 2;
       dcoef.push_back((std::isinf(Ry) || Ry == 0.0) ? 0.0 : 1.0 / Ry);
       dcoef.push_back(1.0 + src[1]);
     } else if (s.geom_kind == OL_GEOM_TOROIDAL) {
-      if (s.n_coeff < 2) return fail(OL_EINVAL, "surface %d: toroidal needs {R_rot, k_yz}", i);
+      if (s.n_coeff < 2) return failf(OL_EINVAL, "surface %d: toroidal needs {R_rot, k_yz}", i);
       const double Rr = src[0], Ryz = s.radius;
       d.n_coeff = s.n_coeff - 2;  // number of y^(2i) terms
       dcoef.push_back(Rr);
@@ -1012,20 +1014,20 @@ void adopt_host_copies(ol_system* sys, Staged& st) {
 int ol_system_create(const ol_surface_desc* surf, int32_t n_surf, const double* coeffs,
                      int32_t n_coeffs, const ol_surface_optics* optics, int32_t n_wavelengths,
                      ol_system** out) {
-  if (!out) return fail(OL_EINVAL, "ol_system_create: out is NULL");
+  if (!out) return failf(OL_EINVAL, "ol_system_create: out is NULL");
   *out = nullptr;
   Staged st;
   if (int rc = stage_system("ol_system_create", surf, n_surf, coeffs, n_coeffs, optics,
                             n_wavelengths, st))
     return rc;
   ol_system* sys = new (std::nothrow) ol_system();
-  if (!sys) return fail(OL_ENOMEM, "ol_system_create: out of host memory");
+  if (!sys) return failf(OL_ENOMEM, "ol_system_create: out of host memory");
   sys->n_surf = n_surf;
   sys->n_wl = n_wavelengths;
   adopt_host_copies(sys, st);
   if (hipGetDevice(&sys->device) != hipSuccess) {
     delete sys;
-    return fail(OL_EHIP, "ol_system_create: no HIP device (hipGetDevice failed)");
+    return failf(OL_EHIP, "ol_system_create: no HIP device (hipGetDevice failed)");
   }
   int rc = upload<float>(st.surf, st.optics, st.coeffs, st.int_slots, sys->f32);
   if (rc == OL_OK) rc = upload<double>(st.surf, st.optics, st.coeffs, st.int_slots, sys->f64);
@@ -1042,11 +1044,11 @@ int ol_system_create(const ol_surface_desc* surf, int32_t n_surf, const double* 
 int ol_system_update(ol_system* sys, const ol_surface_desc* surf, int32_t n_surf,
                      const double* coeffs, int32_t n_coeffs, const ol_surface_optics* optics,
                      int32_t n_wavelengths, void* stream) {
-  if (!sys) return fail(OL_EINVAL, "ol_system_update: system is NULL");
+  if (!sys) return failf(OL_EINVAL, "ol_system_update: system is NULL");
   if (n_surf != sys->n_surf || n_wavelengths != sys->n_wl)
-    return fail(OL_EUNSUPPORTED, "ol_system_update: %d surfaces x %d wavelengths do not fit the "
-                                 "system's %d x %d tables", n_surf, n_wavelengths, sys->n_surf,
-                sys->n_wl);
+    return failf(OL_EUNSUPPORTED, "ol_system_update: %d surfaces x %d wavelengths do not fit the "
+                                  "system's %d x %d tables", n_surf, n_wavelengths, sys->n_surf,
+                 sys->n_wl);
   Staged st;
   if (int rc = stage_system("ol_system_update", surf, n_surf, coeffs, n_coeffs, optics,
                             n_wavelengths, st))
@@ -1054,13 +1056,13 @@ int ol_system_update(ol_system* sys, const ol_surface_desc* surf, int32_t n_surf
   OL_CHECK_CONSISTENT(sys, "ol_system_update");
   const size_t need = st.coeffs.size() ? st.coeffs.size() : 1;
   if (need > sys->f32.coef_capacity || need > sys->f64.coef_capacity)
-    return fail(OL_EUNSUPPORTED, "ol_system_update: coefficient block of %zu values exceeds the "
-                                 "allocated %zu", need, sys->f32.coef_capacity);
+    return failf(OL_EUNSUPPORTED, "ol_system_update: coefficient block of %zu values exceeds the "
+                                  "allocated %zu", need, sys->f32.coef_capacity);
   {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return fail(OL_EINVAL, "ol_system_update: current HIP device %d is not the system's "
-                             "device %d", cur, sys->device);
+      return failf(OL_EINVAL, "ol_system_update: current HIP device %d is not the system's "
+                              "device %d", cur, sys->device);
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   // the fp64 table first: if its copy fails nothing has changed yet and the system stays
@@ -1096,50 +1098,50 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const r
                 int32_t wavelength_index, void* record, int64_t record_stride, void* prt,
                 int32_t first_surface, int32_t last_surface, uint32_t flags, uint32_t* status,
                 const ol_trace_extras* extras, void* stream) {
-  if (!sys) return fail(OL_EINVAL, "ol_trace: system is NULL");
+  if (!sys) return failf(OL_EINVAL, "ol_trace: system is NULL");
   OL_CHECK_CONSISTENT(sys, "ol_trace");
-  if (dt != OL_F32 && dt != OL_F64) return fail(OL_EINVAL, "ol_trace: bad dtype %d", (int)dt);
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_trace: negative ray count");
+  if (dt != OL_F32 && dt != OL_F64) return failf(OL_EINVAL, "ol_trace: bad dtype %d", (int)dt);
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace: negative ray count");
   if (first_surface < 0 || last_surface >= sys->n_surf || first_surface > last_surface)
-    return fail(OL_EINVAL, "ol_trace: surface range [%d, %d] outside [0, %d)", first_surface,
-                last_surface, sys->n_surf);
+    return failf(OL_EINVAL, "ol_trace: surface range [%d, %d] outside [0, %d)", first_surface,
+                 last_surface, sys->n_surf);
   if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return fail(OL_EINVAL, "ol_trace: wavelength index %d outside [0, %d)", wavelength_index,
-                sys->n_wl);
+    return failf(OL_EINVAL, "ol_trace: wavelength index %d outside [0, %d)", wavelength_index,
+                 sys->n_wl);
   if (n_rays == 0) return OL_OK;
   {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return fail(OL_EINVAL, "ol_trace: current HIP device %d is not the system's device %d",
-                  cur, sys->device);
+      return failf(OL_EINVAL, "ol_trace: current HIP device %d is not the system's device %d",
+                   cur, sys->device);
   }
-  if (!rays) return fail(OL_EINVAL, "ol_trace: rays is NULL");
+  if (!rays) return failf(OL_EINVAL, "ol_trace: rays is NULL");
   for (int k = 0; k < 8; ++k)
-    if (!rays[k]) return fail(OL_EINVAL, "ol_trace: rays[%d] is NULL", k);
+    if (!rays[k]) return failf(OL_EINVAL, "ol_trace: rays[%d] is NULL", k);
   if (record && record_stride < n_rays)
-    return fail(OL_EINVAL, "ol_trace: record_stride %lld < n_rays %lld", (long long)record_stride,
-                (long long)n_rays);
+    return failf(OL_EINVAL, "ol_trace: record_stride %lld < n_rays %lld", (long long)record_stride,
+                 (long long)n_rays);
   if (!record && !(flags & OL_TRACE_WRITE_RAYS) && !prt && !(extras && extras->spot_slots))
-    return fail(OL_EINVAL, "ol_trace: nothing to write (no record, no OL_TRACE_WRITE_RAYS)");
+    return failf(OL_EINVAL, "ol_trace: nothing to write (no record, no OL_TRACE_WRITE_RAYS)");
   if (extras && extras->record_first_surface > last_surface)
-    return fail(OL_EINVAL, "ol_trace_ex: record_first_surface %d beyond last_surface %d",
-                extras->record_first_surface, last_surface);
+    return failf(OL_EINVAL, "ol_trace_ex: record_first_surface %d beyond last_surface %d",
+                 extras->record_first_surface, last_surface);
   if (prt && extras && extras->spot_slots)
-    return fail(OL_EINVAL, "ol_trace_ex: the spot epilogue is for unpolarised traces (the "
-                           "polarised intensity needs ol_polarized_intensity first)");
+    return failf(OL_EINVAL, "ol_trace_ex: the spot epilogue is for unpolarised traces (the "
+                            "polarised intensity needs ol_polarized_intensity first)");
   if (!prt) {
     // rays/ray_generator.py:89-94: polarization-dependent coatings need polarized rays
     for (int32_t s = first_surface; s <= last_surface; ++s)
       if (sys->coating[s] >= OL_COAT_FRESNEL)
-        return fail(OL_EINVAL,
-                    "Polarization must be set when surfaces have polarization-dependent "
-                    "coatings.");
+        return failf(OL_EINVAL,
+                     "Polarization must be set when surfaces have polarization-dependent "
+                     "coatings.");
   }
   if (prt && !(flags & OL_TRACE_PRT_COMPLEX)) {
     for (int32_t s = first_surface; s <= last_surface; ++s)
       if (sys->coating[s] == OL_COAT_RETARDER)
-        return fail(OL_EINVAL, "ol_trace: surface %d is a retarder (complex Jones matrix): "
-                               "pass an 18-plane prt with OL_TRACE_PRT_COMPLEX", s);
+        return failf(OL_EINVAL, "ol_trace: surface %d is a retarder (complex Jones matrix): "
+                                "pass an 18-plane prt with OL_TRACE_PRT_COMPLEX", s);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dt == OL_F32)
@@ -1152,31 +1154,31 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const r
 int ol_newton_count(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const rays[8],
                     int32_t wavelength_index, int32_t first_surface, int32_t surface,
                     int32_t* iterations, int32_t verify, void* stream) {
-  if (!sys) return fail(OL_EINVAL, "ol_newton_count: system is NULL");
+  if (!sys) return failf(OL_EINVAL, "ol_newton_count: system is NULL");
   OL_CHECK_CONSISTENT(sys, "ol_newton_count");
   if (dt != OL_F32 && dt != OL_F64)
-    return fail(OL_EINVAL, "ol_newton_count: bad dtype %d", (int)dt);
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_newton_count: negative ray count");
+    return failf(OL_EINVAL, "ol_newton_count: bad dtype %d", (int)dt);
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_newton_count: negative ray count");
   if (first_surface < 0 || surface >= sys->n_surf || first_surface > surface)
-    return fail(OL_EINVAL, "ol_newton_count: surface range [%d, %d] outside [0, %d)",
-                first_surface, surface, sys->n_surf);
+    return failf(OL_EINVAL, "ol_newton_count: surface range [%d, %d] outside [0, %d)",
+                 first_surface, surface, sys->n_surf);
   if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return fail(OL_EINVAL, "ol_newton_count: wavelength index %d outside [0, %d)",
-                wavelength_index, sys->n_wl);
-  if (!iterations) return fail(OL_EINVAL, "ol_newton_count: iterations is NULL");
+    return failf(OL_EINVAL, "ol_newton_count: wavelength index %d outside [0, %d)",
+                 wavelength_index, sys->n_wl);
+  if (!iterations) return failf(OL_EINVAL, "ol_newton_count: iterations is NULL");
   if (!sys->ref_newton[surface])
-    return fail(OL_EINVAL, "ol_newton_count: surface %d is not a traced Newton-Raphson surface "
-                           "with OL_SURF_REFERENCE_NEWTON", surface);
+    return failf(OL_EINVAL, "ol_newton_count: surface %d is not a traced Newton-Raphson surface "
+                            "with OL_SURF_REFERENCE_NEWTON", surface);
   if (n_rays == 0) return OL_OK;
   {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return fail(OL_EINVAL, "ol_newton_count: current HIP device %d is not the system's "
-                             "device %d", cur, sys->device);
+      return failf(OL_EINVAL, "ol_newton_count: current HIP device %d is not the system's "
+                              "device %d", cur, sys->device);
   }
-  if (!rays) return fail(OL_EINVAL, "ol_newton_count: rays is NULL");
+  if (!rays) return failf(OL_EINVAL, "ol_newton_count: rays is NULL");
   for (int k = 0; k < 8; ++k)
-    if (!rays[k]) return fail(OL_EINVAL, "ol_newton_count: rays[%d] is NULL", k);
+    if (!rays[k]) return failf(OL_EINVAL, "ol_newton_count: rays[%d] is NULL", k);
   // the geometry of a ray does not depend on its polarisation: the unpolarised kernel over
   // [first_surface, surface], nothing recorded, nothing written back
   ol_trace_extras ex{};
@@ -1195,59 +1197,59 @@ int ol_trace_generate(const ol_system* sys, ol_dtype dt, int64_t n_rays,
                       int32_t wavelength_index, void* record, int64_t record_stride,
                       void* const rays_out[8], void* prt, uint32_t flags, uint32_t* status,
                       const ol_trace_extras* extras, void* stream) {
-  if (!sys) return fail(OL_EINVAL, "ol_trace_generate: system is NULL");
+  if (!sys) return failf(OL_EINVAL, "ol_trace_generate: system is NULL");
   OL_CHECK_CONSISTENT(sys, "ol_trace_generate");
   if (int rc = refuse_reference_newton("ol_trace_generate", sys)) return rc;
   if (dt != OL_F32 && dt != OL_F64)
-    return fail(OL_EINVAL, "ol_trace_generate: bad dtype %d", (int)dt);
-  if (!p || !in) return fail(OL_EINVAL, "ol_trace_generate: NULL argument");
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_trace_generate: negative ray count");
+    return failf(OL_EINVAL, "ol_trace_generate: bad dtype %d", (int)dt);
+  if (!p || !in) return failf(OL_EINVAL, "ol_trace_generate: NULL argument");
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_generate: negative ray count");
   if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return fail(OL_EINVAL, "ol_trace_generate: wavelength index %d outside [0, %d)",
-                wavelength_index, sys->n_wl);
+    return failf(OL_EINVAL, "ol_trace_generate: wavelength index %d outside [0, %d)",
+                 wavelength_index, sys->n_wl);
   if ((in->vx || in->vy) && !(in->hx && in->hy))
-    return fail(OL_EUNSUPPORTED, "ol_trace_generate: per-ray vignetting planes come with "
-                                 "per-ray field planes (else ol_generate_rays + ol_trace)");
+    return failf(OL_EUNSUPPORTED, "ol_trace_generate: per-ray vignetting planes come with "
+                                  "per-ray field planes (else ol_generate_rays + ol_trace)");
   // (ABI 10: polarised launches take per-ray field planes and apodized pupils too)
   if (extras && extras->spot_slots) {
     if (prt)
-      return fail(OL_EINVAL, "ol_trace_generate: the spot epilogue is for unpolarised traces "
-                             "(the polarised intensity needs update_intensity first)");
+      return failf(OL_EINVAL, "ol_trace_generate: the spot epilogue is for unpolarised traces "
+                              "(the polarised intensity needs update_intensity first)");
     if (in->hx || in->hy || p->apod_kind != OL_APOD_NONE)
-      return fail(OL_EUNSUPPORTED, "ol_trace_generate: the spot epilogue is one field point "
-                                   "without apodization (else ol_trace_spot)");
+      return failf(OL_EUNSUPPORTED, "ol_trace_generate: the spot epilogue is one field point "
+                                    "without apodization (else ol_trace_spot)");
     if (extras->record_first_surface > 0)
-      return fail(OL_EINVAL, "ol_trace_generate: spot epilogue and record_first_surface "
-                             "cannot be combined");
+      return failf(OL_EINVAL, "ol_trace_generate: spot epilogue and record_first_surface "
+                              "cannot be combined");
   }
-  if (!record) return fail(OL_EINVAL, "ol_trace_generate: record is NULL");
+  if (!record) return failf(OL_EINVAL, "ol_trace_generate: record is NULL");
   if (record_stride < n_rays)
-    return fail(OL_EINVAL, "ol_trace_generate: record_stride %lld < n_rays %lld",
-                (long long)record_stride, (long long)n_rays);
+    return failf(OL_EINVAL, "ol_trace_generate: record_stride %lld < n_rays %lld",
+                 (long long)record_stride, (long long)n_rays);
   if (extras && extras->record_first_surface >= sys->n_surf)
-    return fail(OL_EINVAL, "ol_trace_generate: record_first_surface %d outside [0, %d)",
-                extras->record_first_surface, sys->n_surf);
+    return failf(OL_EINVAL, "ol_trace_generate: record_first_surface %d outside [0, %d)",
+                 extras->record_first_surface, sys->n_surf);
   if (rays_out)
     for (int k = 0; k < 8; ++k)
-      if (!rays_out[k]) return fail(OL_EINVAL, "ol_trace_generate: rays_out[%d] is NULL", k);
+      if (!rays_out[k]) return failf(OL_EINVAL, "ol_trace_generate: rays_out[%d] is NULL", k);
   if (!prt) {
     for (int32_t s = 0; s < sys->n_surf; ++s)
       if (sys->coating[s] >= OL_COAT_FRESNEL)
-        return fail(OL_EINVAL,
-                    "Polarization must be set when surfaces have polarization-dependent "
-                    "coatings.");
+        return failf(OL_EINVAL,
+                     "Polarization must be set when surfaces have polarization-dependent "
+                     "coatings.");
   }
   if (prt && !(flags & OL_TRACE_PRT_COMPLEX)) {
     for (int32_t s = 0; s < sys->n_surf; ++s)
       if (sys->coating[s] == OL_COAT_RETARDER)
-        return fail(OL_EINVAL, "ol_trace_generate: surface %d is a retarder (complex Jones "
-                               "matrix): pass an 18-plane prt with OL_TRACE_PRT_COMPLEX", s);
+        return failf(OL_EINVAL, "ol_trace_generate: surface %d is a retarder (complex Jones "
+                                "matrix): pass an 18-plane prt with OL_TRACE_PRT_COMPLEX", s);
   }
   if (n_rays > 0) {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return fail(OL_EINVAL, "ol_trace_generate: current HIP device %d is not the system's "
-                             "device %d", cur, sys->device);
+      return failf(OL_EINVAL, "ol_trace_generate: current HIP device %d is not the system's "
+                              "device %d", cur, sys->device);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dt == OL_F32)
@@ -1260,41 +1262,41 @@ int ol_trace_generate(const ol_system* sys, ol_dtype dt, int64_t n_rays,
 int ol_generate_rays(const ol_raygen_params* p, ol_dtype dt, int64_t n,
                      const ol_raygen_inputs* in, void* const out[8], uint32_t* status,
                      void* stream) {
-  if (!p || !in || !out) return fail(OL_EINVAL, "ol_generate_rays: NULL argument");
-  if (n < 0) return fail(OL_EINVAL, "ol_generate_rays: negative count");
+  if (!p || !in || !out) return failf(OL_EINVAL, "ol_generate_rays: NULL argument");
+  if (n < 0) return failf(OL_EINVAL, "ol_generate_rays: negative count");
   for (int k = 0; k < 7; ++k)
-    if (!out[k] && n > 0) return fail(OL_EINVAL, "ol_generate_rays: out[%d] is NULL", k);
+    if (!out[k] && n > 0) return failf(OL_EINVAL, "ol_generate_rays: out[%d] is NULL", k);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dt == OL_F32) return do_generate_rays<float>(p, n, in, out, status, st);
   if (dt == OL_F64) return do_generate_rays<double>(p, n, in, out, status, st);
-  return fail(OL_EINVAL, "ol_generate_rays: bad dtype %d", (int)dt);
+  return failf(OL_EINVAL, "ol_generate_rays: bad dtype %d", (int)dt);
 }
 
 int ol_trace_spot(const ol_system* sys, ol_dtype dt, int64_t n_rays, const ol_raygen_params* p,
                   const ol_raygen_inputs* in, double cx, double cy, int32_t wavelength_index,
                   void* const hits[3], double* out7, uint32_t* status, void* stream) {
-  if (!sys) return fail(OL_EINVAL, "ol_trace_spot: system is NULL");
+  if (!sys) return failf(OL_EINVAL, "ol_trace_spot: system is NULL");
   OL_CHECK_CONSISTENT(sys, "ol_trace_spot");
   if (int rc = refuse_reference_newton("ol_trace_spot", sys)) return rc;
-  if (dt != OL_F32 && dt != OL_F64) return fail(OL_EINVAL, "ol_trace_spot: bad dtype %d", (int)dt);
-  if (!p || !in || !out7) return fail(OL_EINVAL, "ol_trace_spot: NULL argument");
+  if (dt != OL_F32 && dt != OL_F64) return failf(OL_EINVAL, "ol_trace_spot: bad dtype %d", (int)dt);
+  if (!p || !in || !out7) return failf(OL_EINVAL, "ol_trace_spot: NULL argument");
   if (hits && (!hits[0] || !hits[1] || !hits[2]))
-    return fail(OL_EINVAL, "ol_trace_spot: hits needs three planes");
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_trace_spot: negative ray count");
+    return failf(OL_EINVAL, "ol_trace_spot: hits needs three planes");
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_spot: negative ray count");
   if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return fail(OL_EINVAL, "ol_trace_spot: wavelength index %d outside [0, %d)", wavelength_index,
-                sys->n_wl);
+    return failf(OL_EINVAL, "ol_trace_spot: wavelength index %d outside [0, %d)", wavelength_index,
+                 sys->n_wl);
   if (!(in->flags & OL_SPOT_POLARIZED_OK))
     for (int32_t s = 0; s < sys->n_surf; ++s)
       if (sys->coating[s] >= OL_COAT_FRESNEL)
-        return fail(OL_EINVAL,
-                    "Polarization must be set when surfaces have polarization-dependent "
-                    "coatings.");
+        return failf(OL_EINVAL,
+                     "Polarization must be set when surfaces have polarization-dependent "
+                     "coatings.");
   if (n_rays > 0) {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return fail(OL_EINVAL, "ol_trace_spot: current HIP device %d is not the system's device %d",
-                  cur, sys->device);
+      return failf(OL_EINVAL, "ol_trace_spot: current HIP device %d is not the system's device %d",
+                   cur, sys->device);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dt == OL_F32)
@@ -1308,53 +1310,53 @@ int ol_trace_spot_batch(const ol_system* sys, ol_dtype dt, int64_t n_rays, const
                         const ol_raygen_inputs* in, int32_t n_cells, const ol_spot_cell* cells,
                         void* hits, int64_t hits_stride, double* out8, uint32_t* status,
                         void* stream) {
-  if (!sys) return fail(OL_EINVAL, "ol_trace_spot_batch: system is NULL");
+  if (!sys) return failf(OL_EINVAL, "ol_trace_spot_batch: system is NULL");
   OL_CHECK_CONSISTENT(sys, "ol_trace_spot_batch");
   if (int rc = refuse_reference_newton("ol_trace_spot_batch", sys)) return rc;
   if (dt != OL_F32 && dt != OL_F64)
-    return fail(OL_EINVAL, "ol_trace_spot_batch: bad dtype %d", (int)dt);
+    return failf(OL_EINVAL, "ol_trace_spot_batch: bad dtype %d", (int)dt);
   if (!p || !in || !out8 || (n_cells > 0 && !cells))
-    return fail(OL_EINVAL, "ol_trace_spot_batch: NULL argument");
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_trace_spot_batch: negative ray count");
+    return failf(OL_EINVAL, "ol_trace_spot_batch: NULL argument");
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_spot_batch: negative ray count");
   if (n_cells < 0 || n_cells > OL_SPOT_BATCH_MAX_CELLS)
-    return fail(OL_EINVAL, "ol_trace_spot_batch: %d cells outside [0, %d]", n_cells,
-                OL_SPOT_BATCH_MAX_CELLS);
+    return failf(OL_EINVAL, "ol_trace_spot_batch: %d cells outside [0, %d]", n_cells,
+                 OL_SPOT_BATCH_MAX_CELLS);
   if (in->hx || in->hy || in->vx || in->vy)
-    return fail(OL_EINVAL, "ol_trace_spot_batch: per-ray field / vignetting planes with cells "
-                           "(each cell has ONE field point)");
+    return failf(OL_EINVAL, "ol_trace_spot_batch: per-ray field / vignetting planes with cells "
+                            "(each cell has ONE field point)");
   if (hits && hits_stride < n_rays)
-    return fail(OL_EINVAL, "ol_trace_spot_batch: hits_stride %lld < %lld rays",
-                (long long)hits_stride, (long long)n_rays);
+    return failf(OL_EINVAL, "ol_trace_spot_batch: hits_stride %lld < %lld rays",
+                 (long long)hits_stride, (long long)n_rays);
   for (int32_t c = 0; c < n_cells; ++c) {
     const ol_system* from = cells[c].optics_of ? cells[c].optics_of : sys;
     if (from != sys) {
       OL_CHECK_CONSISTENT(from, "ol_trace_spot_batch (optics_of)");
       if (from->n_surf != sys->n_surf || from->device != sys->device)
-        return fail(OL_EINVAL, "ol_trace_spot_batch: cell %d: optics_of has %d surfaces on device "
-                               "%d, the system %d on device %d", c, from->n_surf, from->device,
-                    sys->n_surf, sys->device);
+        return failf(OL_EINVAL, "ol_trace_spot_batch: cell %d: optics_of has %d surfaces on device "
+                                "%d, the system %d on device %d", c, from->n_surf, from->device,
+                     sys->n_surf, sys->device);
     }
     if (cells[c].wavelength_index < 0 || cells[c].wavelength_index >= from->n_wl)
-      return fail(OL_EINVAL, "ol_trace_spot_batch: cell %d: wavelength index %d outside [0, %d)",
-                  c, cells[c].wavelength_index, from->n_wl);
+      return failf(OL_EINVAL, "ol_trace_spot_batch: cell %d: wavelength index %d outside [0, %d)",
+                   c, cells[c].wavelength_index, from->n_wl);
     if (in->flags & OL_RAYGEN_CHECK_FIELD) {
       auto bad = [](double v) { return !(v >= -1.0 && v <= 1.0); };
       if (bad(cells[c].hx) || bad(cells[c].hy))  // real_ray_tracer.py:156-173, same text
-        return fail(OL_EINVAL, "Normalized field coordinates must be within (-1, 1)");
+        return failf(OL_EINVAL, "Normalized field coordinates must be within (-1, 1)");
     }
   }
   if (!(in->flags & OL_SPOT_POLARIZED_OK))
     for (int32_t s = 0; s < sys->n_surf; ++s)
       if (sys->coating[s] >= OL_COAT_FRESNEL)
-        return fail(OL_EINVAL,
-                    "Polarization must be set when surfaces have polarization-dependent "
-                    "coatings.");
+        return failf(OL_EINVAL,
+                     "Polarization must be set when surfaces have polarization-dependent "
+                     "coatings.");
   if (n_rays > 0 && n_cells > 0) {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return fail(OL_EINVAL,
-                  "ol_trace_spot_batch: current HIP device %d is not the system's device %d", cur,
-                  sys->device);
+      return failf(OL_EINVAL,
+                   "ol_trace_spot_batch: current HIP device %d is not the system's device %d", cur,
+                   sys->device);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dt == OL_F32)
@@ -1368,10 +1370,10 @@ int ol_irradiance(ol_dtype dt, int64_t n_rays, const void* x, const void* y, con
                   const double* x_edges, int32_t nx, const double* y_edges, int32_t ny,
                   double* hist, void* stream) {
   if (!x || !y || !power || !x_edges || !y_edges || !hist)
-    return fail(OL_EINVAL, "ol_irradiance: NULL argument");
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_irradiance: negative count");
+    return failf(OL_EINVAL, "ol_irradiance: NULL argument");
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_irradiance: negative count");
   if (nx < 1 || ny < 1 || (int64_t)nx * ny > (int64_t)1 << 28)
-    return fail(OL_EINVAL, "ol_irradiance: %d x %d bins", nx, ny);
+    return failf(OL_EINVAL, "ol_irradiance: %d x %d bins", nx, ny);
   if (n_rays == 0) return OL_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e;
@@ -1382,8 +1384,8 @@ int ol_irradiance(ol_dtype dt, int64_t n_rays, const void* x, const void* y, con
     e = ol::launch_irradiance<double>(n_rays, (const double*)x, (const double*)y,
                                       (const double*)power, x_edges, nx, y_edges, ny, hist, st);
   else
-    return fail(OL_EINVAL, "ol_irradiance: bad dtype %d", (int)dt);
-  if (e != hipSuccess) return fail(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
+    return failf(OL_EINVAL, "ol_irradiance: bad dtype %d", (int)dt);
+  if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -1391,10 +1393,10 @@ int ol_radial_energy(ol_dtype dt, int64_t n_rays, const void* x, const void* y,
                      const void* intensity, double cx, double cy, const double* r_step,
                      int32_t n_steps, double* bins, void* stream) {
   if (!x || !y || !intensity || !r_step || !bins)
-    return fail(OL_EINVAL, "ol_radial_energy: NULL argument");
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_radial_energy: negative count");
+    return failf(OL_EINVAL, "ol_radial_energy: NULL argument");
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_radial_energy: negative count");
   if (n_steps < 1 || n_steps > 1024)
-    return fail(OL_EINVAL, "ol_radial_energy: n_steps %d outside [1, 1024]", n_steps);
+    return failf(OL_EINVAL, "ol_radial_energy: n_steps %d outside [1, 1024]", n_steps);
   if (n_rays == 0) return OL_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e;
@@ -1406,8 +1408,8 @@ int ol_radial_energy(ol_dtype dt, int64_t n_rays, const void* x, const void* y,
                                          (const double*)intensity, cx, cy, r_step, n_steps, bins,
                                          st);
   else
-    return fail(OL_EINVAL, "ol_radial_energy: bad dtype %d", (int)dt);
-  if (e != hipSuccess) return fail(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
+    return failf(OL_EINVAL, "ol_radial_energy: bad dtype %d", (int)dt);
+  if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -1416,8 +1418,8 @@ int ol_polarized_intensity(ol_dtype dt, int64_t n_rays, const void* prt, int32_t
                            const ol_polarization_state* state, void* intensity,
                            uint32_t* status, void* stream) {
   if (!prt || !k0 || !k0[0] || !k0[1] || !k0[2] || !i0 || !state || !intensity)
-    return fail(OL_EINVAL, "ol_polarized_intensity: NULL argument");
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_polarized_intensity: negative count");
+    return failf(OL_EINVAL, "ol_polarized_intensity: NULL argument");
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_polarized_intensity: negative count");
   if (n_rays == 0) return OL_OK;
   ol::PolStateDev s{state->is_polarized, state->Ex, state->Ey, state->phase_x, state->phase_y};
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1433,9 +1435,9 @@ int ol_polarized_intensity(ol_dtype dt, int64_t n_rays, const void* prt, int32_t
                                          (const double*)i0, s,
                                          (double*)intensity, status, st);
   } else {
-    return fail(OL_EINVAL, "ol_polarized_intensity: bad dtype %d", (int)dt);
+    return failf(OL_EINVAL, "ol_polarized_intensity: bad dtype %d", (int)dt);
   }
-  if (e != hipSuccess) return fail(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -1443,13 +1445,13 @@ int ol_wavefront_opd(const ol_wavefront_params* p, ol_dtype dt, int64_t n_rays,
                      const void* const rays[7], const void* px, const void* py,
                      void* opd_waves, void* const pupil[3], void* stream) {
   if (!p || !rays || !px || !py || !opd_waves)
-    return fail(OL_EINVAL, "ol_wavefront_opd: NULL argument");
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_wavefront_opd: negative count");
+    return failf(OL_EINVAL, "ol_wavefront_opd: NULL argument");
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_wavefront_opd: negative count");
   if (n_rays == 0) return OL_OK;
   for (int k = 0; k < 7; ++k)
-    if (!rays[k]) return fail(OL_EINVAL, "ol_wavefront_opd: rays[%d] is NULL", k);
+    if (!rays[k]) return failf(OL_EINVAL, "ol_wavefront_opd: rays[%d] is NULL", k);
   if (pupil && (!pupil[0] || !pupil[1] || !pupil[2]))
-    return fail(OL_EINVAL, "ol_wavefront_opd: pupil planes must all be given or pupil = NULL");
+    return failf(OL_EINVAL, "ol_wavefront_opd: pupil planes must all be given or pupil = NULL");
   ol::WavefrontDev d{p->xc, p->yc, p->zc, p->R, p->n_image, p->opd_ref,
                      p->ux, p->uy, p->half_epd, p->wavelength_um, p->nx, p->ny, p->nz};
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1469,9 +1471,9 @@ int ol_wavefront_opd(const ol_wavefront_params* p, ol_dtype dt, int64_t n_rays,
     e = ol::launch_wavefront<double>(d, n_rays, r, (const double*)px, (const double*)py,
                                      (double*)opd_waves, pupil ? pu : nullptr, st);
   } else {
-    return fail(OL_EINVAL, "ol_wavefront_opd: bad dtype %d", (int)dt);
+    return failf(OL_EINVAL, "ol_wavefront_opd: bad dtype %d", (int)dt);
   }
-  if (e != hipSuccess) return fail(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -1479,30 +1481,30 @@ int ol_trace_opd(const ol_system* sys, ol_dtype dt, int64_t n_rays, const ol_ray
                  const ol_raygen_inputs* in, const ol_wavefront_params* w,
                  int32_t wavelength_index, void* opd_waves, void* intensity,
                  void* const pupil[3], double* moments12, uint32_t* status, void* stream) {
-  if (!sys) return fail(OL_EINVAL, "ol_trace_opd: system is NULL");
+  if (!sys) return failf(OL_EINVAL, "ol_trace_opd: system is NULL");
   OL_CHECK_CONSISTENT(sys, "ol_trace_opd");
   if (int rc = refuse_reference_newton("ol_trace_opd", sys)) return rc;
   if (dt != OL_F64)
-    return fail(dt == OL_F32 ? OL_EUNSUPPORTED : OL_EINVAL,
-                "ol_trace_opd: wavefront work is fp64 only (dtype %d)", (int)dt);
+    return failf(dt == OL_F32 ? OL_EUNSUPPORTED : OL_EINVAL,
+                 "ol_trace_opd: wavefront work is fp64 only (dtype %d)", (int)dt);
   if (!p || !in || !w || !opd_waves || !intensity || !moments12)
-    return fail(OL_EINVAL, "ol_trace_opd: NULL argument");
+    return failf(OL_EINVAL, "ol_trace_opd: NULL argument");
   if (pupil && (!pupil[0] || !pupil[1] || !pupil[2]))
-    return fail(OL_EINVAL, "ol_trace_opd: pupil planes must all be given or pupil = NULL");
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_trace_opd: negative ray count");
+    return failf(OL_EINVAL, "ol_trace_opd: pupil planes must all be given or pupil = NULL");
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_opd: negative ray count");
   if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return fail(OL_EINVAL, "ol_trace_opd: wavelength index %d outside [0, %d)", wavelength_index,
-                sys->n_wl);
+    return failf(OL_EINVAL, "ol_trace_opd: wavelength index %d outside [0, %d)", wavelength_index,
+                 sys->n_wl);
   for (int32_t s = 0; s < sys->n_surf; ++s)
     if (sys->coating[s] >= OL_COAT_FRESNEL)
-      return fail(OL_EINVAL,
-                  "Polarization must be set when surfaces have polarization-dependent "
-                  "coatings.");
+      return failf(OL_EINVAL,
+                   "Polarization must be set when surfaces have polarization-dependent "
+                   "coatings.");
   if (n_rays > 0) {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return fail(OL_EINVAL, "ol_trace_opd: current HIP device %d is not the system's device %d",
-                  cur, sys->device);
+      return failf(OL_EINVAL, "ol_trace_opd: current HIP device %d is not the system's device %d",
+                   cur, sys->device);
   }
   return do_trace_opd<double>(sys, sys->f64, n_rays, p, in, w, wavelength_index, opd_waves,
                               intensity, pupil, moments12, status,
@@ -1511,27 +1513,27 @@ int ol_trace_opd(const ol_system* sys, ol_dtype dt, int64_t n_rays, const ol_ray
 
 static int opd_common_checks(const char* who, const ol_system* sys, ol_dtype dt,
                              int32_t wavelength_index) {
-  if (!sys) return fail(OL_EINVAL, "%s: system is NULL", who);
+  if (!sys) return failf(OL_EINVAL, "%s: system is NULL", who);
   if (!sys->consistent)
-    return fail(OL_EINVAL, "%s: the system's tables are inconsistent after a failed "
-                           "ol_system_update (destroy it and create a new one)", who);
+    return failf(OL_EINVAL, "%s: the system's tables are inconsistent after a failed "
+                            "ol_system_update (destroy it and create a new one)", who);
   if (dt == OL_F32)
-    return fail(OL_EUNSUPPORTED, "%s: wavefront work is fp64 only (an OPD in waves needs 1e-9 "
-                                 "of the path length)", who);
-  if (dt != OL_F64) return fail(OL_EINVAL, "%s: bad dtype %d", who, (int)dt);
+    return failf(OL_EUNSUPPORTED, "%s: wavefront work is fp64 only (an OPD in waves needs 1e-9 "
+                                  "of the path length)", who);
+  if (dt != OL_F64) return failf(OL_EINVAL, "%s: bad dtype %d", who, (int)dt);
   if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return fail(OL_EINVAL, "%s: wavelength index %d outside [0, %d)", who, wavelength_index,
-                sys->n_wl);
+    return failf(OL_EINVAL, "%s: wavelength index %d outside [0, %d)", who, wavelength_index,
+                 sys->n_wl);
   if (int rc = refuse_reference_newton(who, sys)) return rc;
   for (int32_t s = 0; s < sys->n_surf; ++s)
     if (sys->coating[s] >= OL_COAT_FRESNEL)
-      return fail(OL_EINVAL,
-                  "Polarization must be set when surfaces have polarization-dependent "
-                  "coatings.");
+      return failf(OL_EINVAL,
+                   "Polarization must be set when surfaces have polarization-dependent "
+                   "coatings.");
   int cur = -1;
   if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-    return fail(OL_EINVAL, "%s: current HIP device %d is not the system's device %d", who, cur,
-                sys->device);
+    return failf(OL_EINVAL, "%s: current HIP device %d is not the system's device %d", who, cur,
+                 sys->device);
   return OL_OK;
 }
 
@@ -1541,10 +1543,10 @@ int ol_wavefront_reference(const ol_system* sys, ol_dtype dt, const ol_raygen_pa
                            void* reference_dev, void* chief8, uint32_t* status, void* stream) {
   if (int rc = opd_common_checks("ol_wavefront_reference", sys, dt, wavelength_index)) return rc;
   if (!p || !in || !w || !reference_dev)
-    return fail(OL_EINVAL, "ol_wavefront_reference: NULL argument");
+    return failf(OL_EINVAL, "ol_wavefront_reference: NULL argument");
   if (in->hx || in->hy || in->vx || in->vy)
-    return fail(OL_EINVAL, "ol_wavefront_reference: one field point (launch-uniform field and "
-                           "vignetting)");
+    return failf(OL_EINVAL, "ol_wavefront_reference: one field point (launch-uniform field and "
+                            "vignetting)");
   return do_wavefront_reference<double>(sys, sys->f64, p, in, w, pupil_z, planar,
                                         wavelength_index, reference_dev, chief8, status,
                                         static_cast<hipStream_t>(stream));
@@ -1557,10 +1559,10 @@ int ol_trace_opd_dev(const ol_system* sys, ol_dtype dt, int64_t n_rays,
                      void* stream) {
   if (int rc = opd_common_checks("ol_trace_opd_dev", sys, dt, wavelength_index)) return rc;
   if (!p || !in || !reference_dev || !opd_waves || !intensity || !moments12)
-    return fail(OL_EINVAL, "ol_trace_opd_dev: NULL argument");
+    return failf(OL_EINVAL, "ol_trace_opd_dev: NULL argument");
   if (pupil && (!pupil[0] || !pupil[1] || !pupil[2]))
-    return fail(OL_EINVAL, "ol_trace_opd_dev: pupil needs three planes");
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_trace_opd_dev: negative ray count");
+    return failf(OL_EINVAL, "ol_trace_opd_dev: pupil needs three planes");
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_opd_dev: negative ray count");
   return do_trace_opd<double>(sys, sys->f64, n_rays, p, in, nullptr, wavelength_index, opd_waves,
                               intensity, pupil, moments12, status,
                               static_cast<hipStream_t>(stream), reference_dev);
@@ -1579,17 +1581,17 @@ int ol_wavefront_fit(int32_t kind, const ol_wavefront_params* w, double trim_std
                 OL_FIT_CENTROID == ol::kFitCentroid && OL_FIT_BEST_FIT == ol::kFitBestFit,
                 "header");
   if (!w || !rays || !px || !py || !workspace || !reference_dev || !fit_status)
-    return fail(OL_EINVAL, "ol_wavefront_fit: NULL argument");
+    return failf(OL_EINVAL, "ol_wavefront_fit: NULL argument");
   if (kind != OL_FIT_CENTROID && kind != OL_FIT_BEST_FIT)
-    return fail(OL_EINVAL, "ol_wavefront_fit: unknown kind %d", (int)kind);
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_wavefront_fit: negative count");
+    return failf(OL_EINVAL, "ol_wavefront_fit: unknown kind %d", (int)kind);
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_wavefront_fit: negative count");
   if (flags & ~(uint32_t)(OL_FIT_STD_DDOF1 | OL_FIT_PISTON_SKIPS_NAN))
-    return fail(OL_EINVAL, "ol_wavefront_fit: unknown flags 0x%x", (unsigned)flags);
+    return failf(OL_EINVAL, "ol_wavefront_fit: unknown flags 0x%x", (unsigned)flags);
   if (!(w->n_image > 0.0) || !(w->wavelength_um > 0.0))
-    return fail(OL_EINVAL, "ol_wavefront_fit: n_image %g, wavelength %g", w->n_image,
-                w->wavelength_um);
+    return failf(OL_EINVAL, "ol_wavefront_fit: n_image %g, wavelength %g", w->n_image,
+                 w->wavelength_um);
   for (int k = 0; k < 8; ++k)
-    if (!rays[k]) return fail(OL_EINVAL, "ol_wavefront_fit: rays[%d] is NULL", k);
+    if (!rays[k]) return failf(OL_EINVAL, "ol_wavefront_fit: rays[%d] is NULL", k);
   ol::FitArgs a{};
   a.p.ni = w->n_image;
   a.p.inv_w = 1.0 / (w->wavelength_um * 1e-3);
@@ -1610,7 +1612,7 @@ int ol_wavefront_fit(int32_t kind, const ol_wavefront_params* w, double trim_std
   a.status = fit_status;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e = ol::launch_wavefront_fit(a, st);  // (its first pass writes fit_status)
-  if (e != hipSuccess) return fail(OL_EHIP, "ol_wavefront_fit: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "ol_wavefront_fit: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -1618,17 +1620,17 @@ int ol_wavefront_opd_fitted(int64_t n_rays, const double* const rays[7], const d
                             const double* py, const void* reference_dev, double* opd_waves,
                             double* const pupil[3], void* stream) {
   if (!rays || !px || !py || !reference_dev || !opd_waves)
-    return fail(OL_EINVAL, "ol_wavefront_opd_fitted: NULL argument");
-  if (n_rays < 0) return fail(OL_EINVAL, "ol_wavefront_opd_fitted: negative count");
+    return failf(OL_EINVAL, "ol_wavefront_opd_fitted: NULL argument");
+  if (n_rays < 0) return failf(OL_EINVAL, "ol_wavefront_opd_fitted: negative count");
   for (int k = 0; k < 7; ++k)
-    if (!rays[k]) return fail(OL_EINVAL, "ol_wavefront_opd_fitted: rays[%d] is NULL", k);
+    if (!rays[k]) return failf(OL_EINVAL, "ol_wavefront_opd_fitted: rays[%d] is NULL", k);
   if (pupil && (!pupil[0] || !pupil[1] || !pupil[2]))
-    return fail(OL_EINVAL, "ol_wavefront_opd_fitted: pupil needs three planes");
+    return failf(OL_EINVAL, "ol_wavefront_opd_fitted: pupil needs three planes");
   if (n_rays == 0) return OL_OK;
   hipError_t e = ol::launch_wavefront_fitted(
       static_cast<const ol::WavefrontConsts<double>*>(reference_dev), n_rays, rays, px, py,
       opd_waves, pupil, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(OL_EHIP, "ol_wavefront_opd_fitted: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "ol_wavefront_opd_fitted: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -1637,14 +1639,14 @@ int ol_pupil_fill(ol_dtype dt, int64_t n_rays, const void* opd_waves, const void
                   const int32_t* cell, int32_t n_side, int32_t grid_size, double* grid,
                   void* stream) {
   if (!opd_waves || !intensity || !cell || !grid)
-    return fail(OL_EINVAL, "ol_pupil_fill: NULL argument");
+    return failf(OL_EINVAL, "ol_pupil_fill: NULL argument");
   if ((pupil_x == nullptr) != (pupil_y == nullptr) || (pupil_x && !plane))
-    return fail(OL_EINVAL, "ol_pupil_fill: pupil_x, pupil_y and plane go together");
+    return failf(OL_EINVAL, "ol_pupil_fill: pupil_x, pupil_y and plane go together");
   if (n_rays < 0 || n_side < 1 || grid_size < n_side || grid_size > (1 << 15))
-    return fail(OL_EINVAL, "ol_pupil_fill: n_rays %lld, %d samples per side, grid %d",
-                (long long)n_rays, n_side, grid_size);
+    return failf(OL_EINVAL, "ol_pupil_fill: n_rays %lld, %d samples per side, grid %d",
+                 (long long)n_rays, n_side, grid_size);
   if (n_rays > (int64_t)n_side * n_side)
-    return fail(OL_EINVAL, "ol_pupil_fill: more samples than cells");
+    return failf(OL_EINVAL, "ol_pupil_fill: more samples than cells");
   if (n_rays == 0) return OL_OK;
   const double zero[3] = {0.0, 0.0, 0.0};
   const double* co = plane ? plane : zero;
@@ -1660,8 +1662,8 @@ int ol_pupil_fill(ol_dtype dt, int64_t n_rays, const void* opd_waves, const void
                                       (const double*)pupil_x, (const double*)pupil_y, co, cell,
                                       n_side, grid_size, pad, grid, st);
   else
-    return fail(OL_EINVAL, "ol_pupil_fill: bad dtype %d", (int)dt);
-  if (e != hipSuccess) return fail(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
+    return failf(OL_EINVAL, "ol_pupil_fill: bad dtype %d", (int)dt);
+  if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
@@ -1669,18 +1671,18 @@ int ol_pupil_points(int32_t kind, int32_t param, ol_dtype dt, int64_t n_points,
                     const int32_t* row_first, const int64_t* row_offset, void* x, void* y,
                     void* stream) {
   if (kind != OL_PUPIL_HEXAPOLAR && kind != OL_PUPIL_UNIFORM)
-    return fail(OL_EINVAL, "ol_pupil_points: unknown sampler %d", kind);
+    return failf(OL_EINVAL, "ol_pupil_points: unknown sampler %d", kind);
   if (n_points < 0 || (n_points > 0 && (!x || !y)))
-    return fail(OL_EINVAL, "ol_pupil_points: bad output planes");
+    return failf(OL_EINVAL, "ol_pupil_points: bad output planes");
   if (kind == OL_PUPIL_HEXAPOLAR) {
     if (param < 0 || n_points != 1 + 3 * (int64_t)param * ((int64_t)param + 1))
-      return fail(OL_EINVAL, "ol_pupil_points: %d rings are %lld points, not %lld", param,
-                  (long long)(1 + 3 * (int64_t)param * ((int64_t)param + 1)),
-                  (long long)n_points);
+      return failf(OL_EINVAL, "ol_pupil_points: %d rings are %lld points, not %lld", param,
+                   (long long)(1 + 3 * (int64_t)param * ((int64_t)param + 1)),
+                   (long long)n_points);
   } else {
-    if (param < 2) return fail(OL_EINVAL, "ol_pupil_points: uniform grid side %d < 2", param);
+    if (param < 2) return failf(OL_EINVAL, "ol_pupil_points: uniform grid side %d < 2", param);
     if (n_points > 0 && (!row_first || !row_offset))
-      return fail(OL_EINVAL, "ol_pupil_points: the uniform sampler needs its row tables");
+      return failf(OL_EINVAL, "ol_pupil_points: the uniform sampler needs its row tables");
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e;
@@ -1691,16 +1693,16 @@ int ol_pupil_points(int32_t kind, int32_t param, ol_dtype dt, int64_t n_points,
     e = ol::launch_pupil_points<double>(kind, param, n_points, row_first, row_offset,
                                         static_cast<double*>(x), static_cast<double*>(y), st);
   else
-    return fail(OL_EINVAL, "ol_pupil_points: bad dtype %d", (int)dt);
-  if (e != hipSuccess) return fail(OL_EHIP, "pupil launch failed: %s", hipGetErrorString(e));
+    return failf(OL_EINVAL, "ol_pupil_points: bad dtype %d", (int)dt);
+  if (e != hipSuccess) return failf(OL_EHIP, "pupil launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
 int ol_math_probe(int32_t op, ol_dtype dt, int64_t n, const void* a, const void* b, void* out,
                   void* stream) {
-  if (op < 0 || op > 3) return fail(OL_EINVAL, "ol_math_probe: op must be 0..3");
+  if (op < 0 || op > 3) return failf(OL_EINVAL, "ol_math_probe: op must be 0..3");
   if (n < 0 || (n > 0 && (!a || !out || (op == 1 && !b))))
-    return fail(OL_EINVAL, "ol_math_probe: NULL argument");
+    return failf(OL_EINVAL, "ol_math_probe: NULL argument");
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e;
   if (dt == OL_F32)
@@ -1711,37 +1713,37 @@ int ol_math_probe(int32_t op, ol_dtype dt, int64_t n, const void* a, const void*
                                       static_cast<const double*>(b), static_cast<double*>(out),
                                       st);
   else
-    return fail(OL_EINVAL, "ol_math_probe: bad dtype %d", (int)dt);
-  if (e != hipSuccess) return fail(OL_EHIP, "probe launch failed: %s", hipGetErrorString(e));
+    return failf(OL_EINVAL, "ol_math_probe: bad dtype %d", (int)dt);
+  if (e != hipSuccess) return failf(OL_EHIP, "probe launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
 int ol_stream_fill(void* dst, int64_t bytes, int32_t store_bytes, int32_t planes,
                    uint32_t pattern, void* stream) {
-  if (bytes < 0 || (bytes > 0 && !dst)) return fail(OL_EINVAL, "ol_stream_fill: bad buffer");
-  if (planes < 1) return fail(OL_EINVAL, "ol_stream_fill: planes must be >= 1");
+  if (bytes < 0 || (bytes > 0 && !dst)) return failf(OL_EINVAL, "ol_stream_fill: bad buffer");
+  if (planes < 1) return failf(OL_EINVAL, "ol_stream_fill: planes must be >= 1");
   if (store_bytes != 4 && store_bytes != 8 && store_bytes != 16)
-    return fail(OL_EINVAL, "ol_stream_fill: store_bytes must be 4, 8 or 16");
+    return failf(OL_EINVAL, "ol_stream_fill: store_bytes must be 4, 8 or 16");
   if (bytes % ((int64_t)store_bytes * planes) != 0 ||
       (reinterpret_cast<uintptr_t>(dst) % store_bytes) != 0)
-    return fail(OL_EINVAL, "ol_stream_fill: buffer not a multiple of planes x store_bytes, or "
-                           "not aligned to store_bytes");
+    return failf(OL_EINVAL, "ol_stream_fill: buffer not a multiple of planes x store_bytes, or "
+                            "not aligned to store_bytes");
   hipError_t e = ol::launch_stream_fill(dst, bytes, store_bytes, planes, pattern,
                                         static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(OL_EHIP, "fill launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "fill launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
 int ol_arena_alloc(int64_t bytes, void** out) {
-  if (!out) return fail(OL_EINVAL, "ol_arena_alloc: out is NULL");
+  if (!out) return failf(OL_EINVAL, "ol_arena_alloc: out is NULL");
   *out = nullptr;
-  if (bytes <= 0) return fail(OL_EINVAL, "ol_arena_alloc: %lld bytes", (long long)bytes);
+  if (bytes <= 0) return failf(OL_EINVAL, "ol_arena_alloc: %lld bytes", (long long)bytes);
   void* p = nullptr;
   hipError_t e = hipMalloc(&p, (size_t)bytes);
   if (e != hipSuccess) {
     (void)hipGetLastError();  // (an out-of-memory answer is not a sticky error)
-    return fail(OL_EHIP, "ol_arena_alloc: %lld bytes: %s", (long long)bytes,
-                hipGetErrorString(e));
+    return failf(OL_EHIP, "ol_arena_alloc: %lld bytes: %s", (long long)bytes,
+                 hipGetErrorString(e));
   }
   *out = p;
   return OL_OK;
@@ -1750,35 +1752,35 @@ int ol_arena_alloc(int64_t bytes, void** out) {
 int ol_arena_free(void* arena) {
   if (!arena) return OL_OK;
   hipError_t e = hipFree(arena);
-  if (e != hipSuccess) return fail(OL_EHIP, "ol_arena_free: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "ol_arena_free: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
 int ol_spot_moments(ol_dtype dt, int64_t n_rays, const void* x, const void* y,
                     const void* intensity, double* out6, void* stream) {
-  if (!x || !y || !intensity || !out6) return fail(OL_EINVAL, "ol_spot_moments: NULL argument");
-  if (n_rays <= 0) return n_rays == 0 ? OL_OK : fail(OL_EINVAL, "ol_spot_moments: negative count");
+  if (!x || !y || !intensity || !out6) return failf(OL_EINVAL, "ol_spot_moments: NULL argument");
+  if (n_rays <= 0) return n_rays == 0 ? OL_OK : failf(OL_EINVAL, "ol_spot_moments: negative count");
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e = dt == OL_F32
                      ? ol::launch_spot_moments<float>(n_rays, (const float*)x, (const float*)y,
                                                       (const float*)intensity, out6, st)
                      : ol::launch_spot_moments<double>(n_rays, (const double*)x, (const double*)y,
                                                        (const double*)intensity, out6, st);
-  if (e != hipSuccess) return fail(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 
 int ol_spot_max_r2(ol_dtype dt, int64_t n_rays, const void* x, const void* y,
                    const void* intensity, double cx, double cy, double* out1, void* stream) {
-  if (!x || !y || !intensity || !out1) return fail(OL_EINVAL, "ol_spot_max_r2: NULL argument");
-  if (n_rays <= 0) return n_rays == 0 ? OL_OK : fail(OL_EINVAL, "ol_spot_max_r2: negative count");
+  if (!x || !y || !intensity || !out1) return failf(OL_EINVAL, "ol_spot_max_r2: NULL argument");
+  if (n_rays <= 0) return n_rays == 0 ? OL_OK : failf(OL_EINVAL, "ol_spot_max_r2: negative count");
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e = dt == OL_F32
                      ? ol::launch_spot_max_r2<float>(n_rays, (const float*)x, (const float*)y,
                                                      (const float*)intensity, cx, cy, out1, st)
                      : ol::launch_spot_max_r2<double>(n_rays, (const double*)x, (const double*)y,
                                                       (const double*)intensity, cx, cy, out1, st);
-  if (e != hipSuccess) return fail(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
 

@@ -22,10 +22,9 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
 #include "../../include/optiland_hip.h"
+#include "analysis_device.h"
 #include "last_error.h"
 
 // (namespace ol, not an anonymous one: tools/asm_stats.py and rocprofv3 name the kernels)
@@ -45,15 +44,6 @@ struct alignas(16) HuygensRay {
 };
 static_assert(sizeof(HuygensRay) == 64, "one 64-byte record per pupil sample");
 
-static int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return set_last_error(code, buf);
-}
-
 // a + b = s + e and a - b = s + e exactly (Knuth's TwoSum; no operation here may be contracted
 // or reassociated, and none is: contraction only fuses a product into a sum)
 __device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {
@@ -67,12 +57,6 @@ __device__ __forceinline__ void two_diff(double a, double b, double& s, double& 
   e = (a - (s - bb)) - (b + bb);
 }
 
-// (cos, sin) of 2 pi t, the phase t in cycles: t - rint(t) is exact, so sincospi sees |x| <= 1
-__device__ __forceinline__ void cis_cycles(double t, double& c, double& s) {
-  const double f = t - rint(t);
-  sincospi(2.0 * f, &s, &c);
-}
-
 __global__ __launch_bounds__(kBlock) void huygens_rays_kernel(
     int64_t n, const double* __restrict__ x, const double* __restrict__ y,
     const double* __restrict__ z, const double* __restrict__ amp,
@@ -81,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void huygens_rays_kernel(
   for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n;
        j += (int64_t)gridDim.x * kBlock) {
     double c, s;
-    cis_cycles(-opd[j] * inv_wl, c, s);
+    sincospi(2.0 * phase_cycles(-opd[j] * inv_wl), &s, &c);
     const double ar = amp[j], ai = amp_imag ? amp_imag[j] : 0.0;
     HuygensRay r;
     r.u = x[j];
@@ -150,7 +134,7 @@ __global__ __launch_bounds__(kBlock) void huygens_partial_kernel(
       const double t = R * inv_wl;
       const double t_lo = fma(R, inv_wl, -t) + fma(R, inv_wl_lo, (d * h) * inv_wl);
       double c, s;
-      sincospi(2.0 * ((t - rint(t)) + t_lo), &s, &c);
+      sincospi(2.0 * phase_cycles(t, t_lo), &s, &c);
       // obliquity 1/2 (1 + cos theta), cos theta = (P - Q) . Q / (Rp R), and the 1/R of the
       // spherical wave
       const double dot = fma(dx, r.nx, fma(dy, r.ny, dz * r.nz));
@@ -201,21 +185,21 @@ extern "C" int ol_huygens_psf(int64_t n_pupil, const double* const pupil[5],
                               const double* amp_imag, int64_t n_image,
                               const double* const image[3], double wavelength_mm, double Rp,
                               double* psf_out, double* field_out, void* stream) {
-  if (!pupil || !image) return fail(OL_EINVAL, "ol_huygens_psf: NULL argument");
+  if (!pupil || !image) return failf(OL_EINVAL, "ol_huygens_psf: NULL argument");
   if (n_pupil < 0 || n_image < 0)
-    return fail(OL_EINVAL, "ol_huygens_psf: negative count (n_pupil %lld, n_image %lld)",
-                (long long)n_pupil, (long long)n_image);
+    return failf(OL_EINVAL, "ol_huygens_psf: negative count (n_pupil %lld, n_image %lld)",
+                 (long long)n_pupil, (long long)n_image);
   if (!(wavelength_mm > 0.0) || std::isinf(wavelength_mm))
-    return fail(OL_EINVAL, "ol_huygens_psf: wavelength %g mm must be positive", wavelength_mm);
+    return failf(OL_EINVAL, "ol_huygens_psf: wavelength %g mm must be positive", wavelength_mm);
   if (Rp == 0.0 || std::isnan(Rp))
-    return fail(OL_EINVAL, "ol_huygens_psf: reference sphere radius Rp %g must be non-zero", Rp);
+    return failf(OL_EINVAL, "ol_huygens_psf: reference sphere radius Rp %g must be non-zero", Rp);
   if (n_image == 0) return OL_OK;
-  if (!psf_out) return fail(OL_EINVAL, "ol_huygens_psf: psf_out is NULL");
+  if (!psf_out) return failf(OL_EINVAL, "ol_huygens_psf: psf_out is NULL");
   for (int k = 0; k < 3; ++k)
-    if (!image[k]) return fail(OL_EINVAL, "ol_huygens_psf: image[%d] is NULL", k);
+    if (!image[k]) return failf(OL_EINVAL, "ol_huygens_psf: image[%d] is NULL", k);
   if (n_pupil > 0)
     for (int k = 0; k < 5; ++k)
-      if (!pupil[k]) return fail(OL_EINVAL, "ol_huygens_psf: pupil[%d] is NULL", k);
+      if (!pupil[k]) return failf(OL_EINVAL, "ol_huygens_psf: pupil[%d] is NULL", k);
 
   hipStream_t st = (hipStream_t)stream;
   const int64_t tiles = (n_image + kTile - 1) / kTile;
@@ -229,15 +213,10 @@ extern "C" int ol_huygens_psf(int64_t n_pupil, const double* const pupil[5],
   }
   const size_t ray_bytes = (size_t)n_pupil * sizeof(HuygensRay);
   const size_t bytes = ray_bytes + (size_t)n_split * (size_t)n_image * 2 * sizeof(double);
-  void* ws = nullptr;
-  if (bytes) {
-    hipError_t e = hipMallocAsync(&ws, bytes, st);
-    if (e != hipSuccess)
-      return fail(e == hipErrorOutOfMemory ? OL_ENOMEM : OL_EHIP,
-                  "ol_huygens_psf: workspace of %zu bytes: %s", bytes, hipGetErrorString(e));
-  }
-  HuygensRay* rays = (HuygensRay*)ws;
-  double* partial = (double*)((char*)ws + ray_bytes);
+  Workspace ws{"ol_huygens_psf", st};
+  if (int rc = ws.alloc(bytes)) return rc;  // (nothing to sum: no bytes, no allocation)
+  HuygensRay* rays = (HuygensRay*)ws.ptr;
+  double* partial = (double*)((char*)ws.ptr + ray_bytes);
   const double inv_wl = 1.0 / wavelength_mm;  // 1 / lambda = inv_wl + inv_wl_lo
   const double inv_wl_lo = -std::fma(wavelength_mm, inv_wl, -1.0) / wavelength_mm;
   if (n_pupil > 0) {
@@ -250,12 +229,5 @@ extern "C" int ol_huygens_psf(int64_t n_pupil, const double* const pupil[5],
   }
   hipLaunchKernelGGL(huygens_finish_kernel, dim3(grid_for(n_image)), dim3(kBlock), 0, st,
                      n_image, n_split, (const double*)partial, psf_out, field_out);
-  hipError_t e = hipGetLastError();
-  if (ws) {
-    const hipError_t f = hipFreeAsync(ws, st);
-    if (e == hipSuccess) e = f;
-  }
-  if (e != hipSuccess)
-    return fail(OL_EHIP, "ol_huygens_psf: launch failed: %s", hipGetErrorString(e));
-  return OL_OK;
+  return ws.finish();
 }

@@ -27,11 +27,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <limits>
 
 #include "../../include/optiland_hip.h"
+#include "analysis_device.h"
 #include "last_error.h"
 
 // (namespace ol, not an anonymous one: tools/asm_stats.py and rocprofv3 name the kernels)
@@ -54,15 +53,6 @@ struct MtfPartial {
   double lo, hi;
   int32_t bad, pad_;
 };
-
-static int mtf_fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return set_last_error(code, buf);
-}
 
 // np.linspace(lo, hi, n_bins + 1)[j]: j * step + lo with the product rounded BEFORE the sum
 // (numpy/_core/function_base.py: `y = y * step; y += start`; a step that underflowed to 0:
@@ -108,7 +98,7 @@ __global__ __launch_bounds__(kMtfBlock) void mtf_range_kernel(MtfCurves curves, 
   for (int64_t i = (int64_t)blockIdx.x * kMtfBlock + tid; i < n;
        i += (int64_t)gridDim.x * kMtfBlock) {
     const double v = (double)x[i];
-    bad |= !(fabs(v) <= std::numeric_limits<double>::max());  // NaN or +-inf
+    bad |= !is_finite(v);
     lo = fmin(lo, v);
     hi = fmax(hi, v);
   }
@@ -158,6 +148,8 @@ __global__ __launch_bounds__(kMtfBlock) void mtf_histogram_kernel(
     s_bad[tid] = p.bad;
   }
   for (int j = tid; j < n_bins; j += kMtfBlock) s_bins[j] = 0;
+  // (the fold of mtf_range_kernel, written out a second time: behind one inline function the
+  // compiler lays this kernel's blocks out differently, and its code is no longer the measured one)
   __syncthreads();
   for (int w = kMtfBlock / 2; w > 0; w >>= 1) {
     if (tid < w) {
@@ -230,11 +222,11 @@ __global__ __launch_bounds__(kMtfBlock) void mtf_transform_kernel(
     __syncthreads();
     for (int i = sl; i < m; i += kSlice) {
       const double a = s_a[i], d = s_d[i];
-      // the phase in cycles as t + t_lo; t - rint(t) is exact, so sincospi sees |x| <= 1
+      // the phase in cycles as t + t_lo
       const double t = v * d;
       const double t_lo = fma(v, d, -t);
       double sn, cs;
-      sincospi(2.0 * ((t - rint(t)) + t_lo), &sn, &cs);
+      sincospi(2.0 * phase_cycles(t, t_lo), &sn, &cs);
       re = fma(a, cs, re);
       im = fma(a, sn, im);
       total += a;  // (integers below 2^53: exact)
@@ -284,33 +276,33 @@ extern "C" int ol_geometric_mtf(ol_dtype dt, int32_t n_curves, const void* const
                                 int32_t* counts_out, double* edges_minmax_out,
                                 int32_t* flags_out, void* stream) {
   if (dt != OL_F32 && dt != OL_F64)
-    return mtf_fail(OL_EINVAL, "ol_geometric_mtf: dtype %d is neither OL_F32 nor OL_F64", (int)dt);
+    return failf(OL_EINVAL, "ol_geometric_mtf: dtype %d is neither OL_F32 nor OL_F64", (int)dt);
   if (n_curves < 0 || n_curves > OL_MTF_MAX_CURVES)
-    return mtf_fail(OL_EINVAL, "ol_geometric_mtf: n_curves %d is outside 0..%d", (int)n_curves,
-                    OL_MTF_MAX_CURVES);
+    return failf(OL_EINVAL, "ol_geometric_mtf: n_curves %d is outside 0..%d", (int)n_curves,
+                 OL_MTF_MAX_CURVES);
   if (num_points < 0)
-    return mtf_fail(OL_EINVAL, "ol_geometric_mtf: negative count (num_points %d)",
-                    (int)num_points);
+    return failf(OL_EINVAL, "ol_geometric_mtf: negative count (num_points %d)",
+                 (int)num_points);
   if (n_bins < 1 || n_bins > OL_MTF_MAX_BINS)
-    return mtf_fail(OL_EINVAL, "ol_geometric_mtf: n_bins %d is outside 1..%d", (int)n_bins,
-                    OL_MTF_MAX_BINS);
+    return failf(OL_EINVAL, "ol_geometric_mtf: n_bins %d is outside 1..%d", (int)n_bins,
+                 OL_MTF_MAX_BINS);
   if (n_curves == 0) return OL_OK;
-  if (!coords || !lengths) return mtf_fail(OL_EINVAL, "ol_geometric_mtf: NULL argument");
+  if (!coords || !lengths) return failf(OL_EINVAL, "ol_geometric_mtf: NULL argument");
   if (!edges_minmax_out || !flags_out)
-    return mtf_fail(OL_EINVAL, "ol_geometric_mtf: edges_minmax_out / flags_out is NULL");
+    return failf(OL_EINVAL, "ol_geometric_mtf: edges_minmax_out / flags_out is NULL");
   if (num_points > 0 && (!freq || !mtf_out))
-    return mtf_fail(OL_EINVAL, "ol_geometric_mtf: freq / mtf_out is NULL");
+    return failf(OL_EINVAL, "ol_geometric_mtf: freq / mtf_out is NULL");
   MtfCurves curves = {};
   int64_t longest = 0;
   for (int c = 0; c < n_curves; ++c) {
     if (lengths[c] < 0)
-      return mtf_fail(OL_EINVAL, "ol_geometric_mtf: negative count (lengths[%d] = %lld)", c,
-                      (long long)lengths[c]);
+      return failf(OL_EINVAL, "ol_geometric_mtf: negative count (lengths[%d] = %lld)", c,
+                   (long long)lengths[c]);
     if (lengths[c] > (int64_t)std::numeric_limits<int32_t>::max())
-      return mtf_fail(OL_EINVAL, "ol_geometric_mtf: lengths[%d] = %lld does not fit the int32 bins",
-                      c, (long long)lengths[c]);
+      return failf(OL_EINVAL, "ol_geometric_mtf: lengths[%d] = %lld does not fit the int32 bins",
+                   c, (long long)lengths[c]);
     if (lengths[c] > 0 && !coords[c])
-      return mtf_fail(OL_EINVAL, "ol_geometric_mtf: coords[%d] is NULL", c);
+      return failf(OL_EINVAL, "ol_geometric_mtf: coords[%d] is NULL", c);
     curves.x[c] = coords[c];
     curves.n[c] = lengths[c];
     longest = std::max(longest, lengths[c]);
@@ -322,23 +314,15 @@ extern "C" int ol_geometric_mtf(ol_dtype dt, int32_t n_curves, const void* const
   const size_t partial_bytes = (size_t)n_curves * slabs * sizeof(MtfPartial);
   const size_t bytes =
       partial_bytes + (counts_out ? 0 : (size_t)n_curves * (size_t)n_bins * sizeof(int32_t));
-  void* ws = nullptr;
-  hipError_t e = hipMallocAsync(&ws, bytes, st);
-  if (e != hipSuccess)
-    return mtf_fail(e == hipErrorOutOfMemory ? OL_ENOMEM : OL_EHIP,
-                    "ol_geometric_mtf: workspace of %zu bytes: %s", bytes, hipGetErrorString(e));
-  MtfPartial* partial = (MtfPartial*)ws;
-  int32_t* counts = counts_out ? counts_out : (int32_t*)((char*)ws + partial_bytes);
+  Workspace ws{"ol_geometric_mtf", st};
+  if (int rc = ws.alloc(bytes)) return rc;
+  MtfPartial* partial = (MtfPartial*)ws.ptr;
+  int32_t* counts = counts_out ? counts_out : (int32_t*)((char*)ws.ptr + partial_bytes);
   if (dt == OL_F32)
     mtf_launch<float>(curves, n_curves, slabs, n_bins, num_points, freq, scale, partial, counts,
                       mtf_out, edges_minmax_out, flags_out, st);
   else
     mtf_launch<double>(curves, n_curves, slabs, n_bins, num_points, freq, scale, partial, counts,
                        mtf_out, edges_minmax_out, flags_out, st);
-  e = hipGetLastError();
-  const hipError_t f = hipFreeAsync(ws, st);
-  if (e == hipSuccess) e = f;
-  if (e != hipSuccess)
-    return mtf_fail(OL_EHIP, "ol_geometric_mtf: launch failed: %s", hipGetErrorString(e));
-  return OL_OK;
+  return ws.finish();
 }

@@ -44,11 +44,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <limits>
 
 #include "../../include/optiland_hip.h"
+#include "analysis_device.h"
 #include "last_error.h"
 
 // (namespace ol, not an anonymous one: tools/asm_stats.py and rocprofv3 name the kernels)
@@ -70,19 +69,6 @@ struct ZkTable {
   const double* __restrict__ tf;   // K x kZkStride: norm, c_0 (highest power) ... c_s
   int K;
 };
-
-static int zk_fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return set_last_error(code, buf);
-}
-
-__device__ __forceinline__ bool zk_finite(double v) {
-  return fabs(v) <= std::numeric_limits<double>::max();
-}
 
 // emit(column, Z_column(x, y)) for every term of the table.  The table lives in device memory:
 // a column, a coefficient count or an |m| outside its range is clamped, so that a damaged
@@ -150,7 +136,7 @@ __global__ __launch_bounds__(kZkBlock) void zk_gram_kernel(
       if (valid && intensity) valid = intensity[i] > 0.0;
       if (valid) {
         const double px = x[i], py = y[i], pz = z[i];
-        bad |= !(zk_finite(px) && zk_finite(py) && zk_finite(pz));
+        bad |= !(is_finite(px) && is_finite(py) && is_finite(pz));
         ++count;
         if (kResidual) {
           double w = 0.0;
@@ -370,10 +356,10 @@ __global__ __launch_bounds__(kZkBlock) void smtf_kernel(
     const double xs = x[i] - dx, ys = y[i] - dy;
     if (smtf_outside(xs, ys)) continue;  // sampled.py:190-193 (a NaN stays in)
     const double amp = sqrt(w);
-    // the phase in cycles; t - rint(t) is exact, so sincospi sees |argument| <= 1
+    // the phase in cycles
     const double t = (p1 ? 0.0 : opd[i]) - zk_sum(tb, coeffs, xs, ys);
     double sn, cs;
-    sincospi(2.0 * (t - rint(t)), &sn, &cs);
+    sincospi(2.0 * phase_cycles(t), &sn, &cs);
     if (p1) {  // (uniform) a pupil function the caller supplies: P1 sqrt(I) exp(-2 pi i W)
       const double pr = p1[2 * i], pj = p1[2 * i + 1];
       re += amp * (pr * cs - pj * sn);
@@ -432,16 +418,16 @@ __global__ __launch_bounds__(kZkBlock) void smtf_finish_kernel(int n_freq, int c
 static int zk_check_table(const char* who, int32_t num_terms, const int32_t* term_i,
                           const double* term_f) {
   if (num_terms < 1 || num_terms > OL_ZK_MAX_TERMS)
-    return zk_fail(OL_EINVAL, "%s: num_terms %d is outside 1..%d (OL_ZK_MAX_TERMS)", who,
-                   (int)num_terms, OL_ZK_MAX_TERMS);
-  if (!term_i || !term_f) return zk_fail(OL_EINVAL, "%s: the term table is NULL", who);
+    return failf(OL_EINVAL, "%s: num_terms %d is outside 1..%d (OL_ZK_MAX_TERMS)", who,
+                 (int)num_terms, OL_ZK_MAX_TERMS);
+  if (!term_i || !term_f) return failf(OL_EINVAL, "%s: the term table is NULL", who);
   return OL_OK;
 }
 
 static int zk_check_count(const char* who, int64_t n) {
-  if (n < 0) return zk_fail(OL_EINVAL, "%s: negative count (n = %lld)", who, (long long)n);
+  if (n < 0) return failf(OL_EINVAL, "%s: negative count (n = %lld)", who, (long long)n);
   if (n > (int64_t)std::numeric_limits<int32_t>::max())
-    return zk_fail(OL_EINVAL, "%s: n = %lld is above INT32_MAX", who, (long long)n);
+    return failf(OL_EINVAL, "%s: n = %lld is above INT32_MAX", who, (long long)n);
   return OL_OK;
 }
 
@@ -456,8 +442,8 @@ extern "C" int ol_zernike_fit(int32_t num_terms, const int32_t* term_i, const do
   if (int rc = zk_check_table("ol_zernike_fit", num_terms, term_i, term_f)) return rc;
   if (int rc = zk_check_count("ol_zernike_fit", n)) return rc;
   if (!coeffs_out || !status_out)
-    return zk_fail(OL_EINVAL, "ol_zernike_fit: coeffs_out / status_out is NULL");
-  if (n > 0 && (!x || !y || !z)) return zk_fail(OL_EINVAL, "ol_zernike_fit: x / y / z is NULL");
+    return failf(OL_EINVAL, "ol_zernike_fit: coeffs_out / status_out is NULL");
+  if (n > 0 && (!x || !y || !z)) return failf(OL_EINVAL, "ol_zernike_fit: x / y / z is NULL");
 
   hipStream_t st = (hipStream_t)stream;
   const int K = num_terms, M = K + 1;
@@ -467,13 +453,9 @@ extern "C" int ol_zernike_fit(int32_t num_terms, const int32_t* term_i, const do
   // workspace (doubles): partials | merged triangle | factor and scale | block and merged meta
   const size_t n_partial = (size_t)blocks * entries;
   const size_t doubles = n_partial + entries + tri + K + 2 * (size_t)blocks + 2;
-  void* ws = nullptr;
-  hipError_t e = hipMallocAsync(&ws, doubles * sizeof(double), st);
-  if (e != hipSuccess)
-    return zk_fail(e == hipErrorOutOfMemory ? OL_ENOMEM : OL_EHIP,
-                   "ol_zernike_fit: workspace of %zu bytes: %s", doubles * sizeof(double),
-                   hipGetErrorString(e));
-  double* partial = (double*)ws;
+  Workspace ws{"ol_zernike_fit", st};
+  if (int rc = ws.alloc(doubles * sizeof(double))) return rc;
+  double* partial = (double*)ws.ptr;
   double* gram = partial + n_partial;
   double* factor = gram + entries;
   int64_t* meta = (int64_t*)(factor + tri + K);
@@ -493,12 +475,7 @@ extern "C" int ol_zernike_fit(int32_t num_terms, const int32_t* term_i, const do
   hipLaunchKernelGGL(zk_refine_kernel, dim3(1), dim3(kZkBlock), 0, st, K, blocks,
                      (const double*)partial, (const double*)factor, coeffs_out,
                      (const int32_t*)status_out);
-  e = hipGetLastError();
-  const hipError_t f = hipFreeAsync(ws, st);
-  if (e == hipSuccess) e = f;
-  if (e != hipSuccess)
-    return zk_fail(OL_EHIP, "ol_zernike_fit: launch failed: %s", hipGetErrorString(e));
-  return OL_OK;
+  return ws.finish();
 }
 
 extern "C" int ol_zernike_eval(int32_t num_terms, const int32_t* term_i, const double* term_f,
@@ -506,17 +483,14 @@ extern "C" int ol_zernike_eval(int32_t num_terms, const int32_t* term_i, const d
                                double* out, void* stream) {
   if (int rc = zk_check_table("ol_zernike_eval", num_terms, term_i, term_f)) return rc;
   if (int rc = zk_check_count("ol_zernike_eval", n)) return rc;
-  if (!coeffs) return zk_fail(OL_EINVAL, "ol_zernike_eval: coeffs is NULL");
+  if (!coeffs) return failf(OL_EINVAL, "ol_zernike_eval: coeffs is NULL");
   if (n == 0) return OL_OK;
-  if (!x || !y || !out) return zk_fail(OL_EINVAL, "ol_zernike_eval: x / y / out is NULL");
+  if (!x || !y || !out) return failf(OL_EINVAL, "ol_zernike_eval: x / y / out is NULL");
   const ZkTable tb = {term_i, term_f, num_terms};
   const unsigned blocks = (unsigned)std::min<int64_t>((n + kZkBlock - 1) / kZkBlock, 4096);
   hipLaunchKernelGGL(zk_eval_kernel, dim3(blocks), dim3(kZkBlock), 0, (hipStream_t)stream, tb,
                      coeffs, n, x, y, out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return zk_fail(OL_EHIP, "ol_zernike_eval: launch failed: %s", hipGetErrorString(e));
-  return OL_OK;
+  return Workspace{"ol_zernike_eval", (hipStream_t)stream}.finish();  // (no workspace)
 }
 
 extern "C" int ol_sampled_mtf(int32_t num_terms, const int32_t* term_i, const double* term_f,
@@ -527,34 +501,26 @@ extern "C" int ol_sampled_mtf(int32_t num_terms, const int32_t* term_i, const do
   if (int rc = zk_check_table("ol_sampled_mtf", num_terms, term_i, term_f)) return rc;
   if (int rc = zk_check_count("ol_sampled_mtf", n)) return rc;
   if (n_freq < 0 || n_freq > OL_SMTF_MAX_FREQ)
-    return zk_fail(OL_EINVAL, "ol_sampled_mtf: n_freq %d is outside 0..%d", (int)n_freq,
-                   OL_SMTF_MAX_FREQ);
-  if (!coeffs) return zk_fail(OL_EINVAL, "ol_sampled_mtf: coeffs is NULL");
+    return failf(OL_EINVAL, "ol_sampled_mtf: n_freq %d is outside 0..%d", (int)n_freq,
+                 OL_SMTF_MAX_FREQ);
+  if (!coeffs) return failf(OL_EINVAL, "ol_sampled_mtf: coeffs is NULL");
   if (n_freq == 0) return OL_OK;
-  if (!shifts || !mtf_out) return zk_fail(OL_EINVAL, "ol_sampled_mtf: shifts / mtf_out is NULL");
+  if (!shifts || !mtf_out) return failf(OL_EINVAL, "ol_sampled_mtf: shifts / mtf_out is NULL");
   if (n > 0 && (!x || !y || !intensity))
-    return zk_fail(OL_EINVAL, "ol_sampled_mtf: x / y / intensity is NULL");
+    return failf(OL_EINVAL, "ol_sampled_mtf: x / y / intensity is NULL");
   if (n > 0 && !opd_waves && !p1)
-    return zk_fail(OL_EINVAL, "ol_sampled_mtf: neither opd_waves nor p1 is given");
+    return failf(OL_EINVAL, "ol_sampled_mtf: neither opd_waves nor p1 is given");
 
   hipStream_t st = (hipStream_t)stream;
   const int chunks = (int)std::max<int64_t>(
       1, std::min<int64_t>((n + kZkBlock - 1) / kZkBlock, kSmtfMaxChunks));
   const size_t bytes = (size_t)n_freq * chunks * 3 * sizeof(double);
-  void* ws = nullptr;
-  hipError_t e = hipMallocAsync(&ws, bytes, st);
-  if (e != hipSuccess)
-    return zk_fail(e == hipErrorOutOfMemory ? OL_ENOMEM : OL_EHIP,
-                   "ol_sampled_mtf: workspace of %zu bytes: %s", bytes, hipGetErrorString(e));
+  Workspace ws{"ol_sampled_mtf", st};
+  if (int rc = ws.alloc(bytes)) return rc;
   const ZkTable tb = {term_i, term_f, num_terms};
   hipLaunchKernelGGL(smtf_kernel, dim3((unsigned)chunks, (unsigned)n_freq), dim3(kZkBlock), 0, st,
-                     tb, coeffs, n, x, y, opd_waves, p1, intensity, shifts, (double*)ws);
+                     tb, coeffs, n, x, y, opd_waves, p1, intensity, shifts, (double*)ws.ptr);
   hipLaunchKernelGGL(smtf_finish_kernel, dim3((n_freq + kZkBlock - 1) / kZkBlock), dim3(kZkBlock),
-                     0, st, (int)n_freq, chunks, (const double*)ws, mtf_out, otf_out);
-  e = hipGetLastError();
-  const hipError_t f = hipFreeAsync(ws, st);
-  if (e == hipSuccess) e = f;
-  if (e != hipSuccess)
-    return zk_fail(OL_EHIP, "ol_sampled_mtf: launch failed: %s", hipGetErrorString(e));
-  return OL_OK;
+                     0, st, (int)n_freq, chunks, (const double*)ws.ptr, mtf_out, otf_out);
+  return ws.finish();
 }

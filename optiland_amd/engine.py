@@ -1579,6 +1579,43 @@ class HipSystem:
         return huygens_sum(*args, device=self.device, **kwargs)
 
 
+def _analysis_library(has, symbols: str):
+    """The loaded library if `has` finds its entry points in it, else the way to get them."""
+    lib = _capi.load()
+    if not has(lib):
+        raise _capi.HipExtensionError(
+            f"{_capi.library_path()} has no {symbols}; rebuild the library "
+            "(`python -c 'import __graft_entry__ as g; g.build()'`)")
+    return lib
+
+
+def _shape(v):
+    return tuple(v.shape) if hasattr(v, "shape") else tuple(np.shape(v))
+
+
+def _real(who, name, v):
+    if isinstance(v, torch.Tensor) and (v.is_complex() or not v.is_floating_point()):
+        raise ValueError(f"{who}: {name} must be real floating point, got {v.dtype}")
+
+
+def _same_size(who, names, arrays):
+    sizes = [int(np.prod(_shape(v), dtype=np.int64)) for v in arrays]
+    if any(s != sizes[0] for s in sizes):
+        raise ValueError(f"{who}: " + " / ".join(names) + f" differ in size ({sizes})")
+    return sizes[0]
+
+
+def _points(who, names, arrays):
+    """Host-side checks of same-sized real point arrays (nothing here touches a device): n."""
+    for name, v in zip(names, arrays):
+        _real(who, name, v)
+    return _same_size(who, names, arrays)
+
+
+def _f64_plane(v, dev):
+    return torch.as_tensor(v, device=dev).detach().to(torch.float64).reshape(-1).contiguous()
+
+
 def huygens_sum(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd_mm,
                 wavelength_mm: float, Rp: float, *, want_field: bool = False, device=None):
     """`ol_huygens_psf`: the Huygens-Fresnel sum of psf/huygens_fresnel_strategies.py:97-172 on
@@ -1589,24 +1626,18 @@ def huygens_sum(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd_m
     Returns psf = |field|^2 (float64, image_x's shape) or, with `want_field`, (psf, field)
     with field complex128.  Tensors on another device are copied to `device` (default: the
     current HIP device); host arrays are accepted too."""
-    lib = _capi.load()
-    if not _capi.has_huygens(lib):
-        raise _capi.HipExtensionError(
-            f"{_capi.library_path()} has no ol_huygens_psf; rebuild the library "
-            "(`python -c 'import __graft_entry__ as g; g.build()'`)")
+    lib = _analysis_library(_capi.has_huygens, "ol_huygens_psf")
     dev = _require_gpu(device)
 
     def plane(v):
         t = torch.as_tensor(v, device=dev)
         if t.is_complex():
             raise ValueError("huygens_sum: only the amplitude may be complex")
-        return t.to(torch.float64).reshape(-1).contiguous()
+        return _f64_plane(t, dev)
 
-    shape = tuple(torch.as_tensor(image_x).shape)
+    shape = _shape(torch.as_tensor(image_x))
     img = [plane(v) for v in (image_x, image_y, image_z)]
-    m = img[0].numel()
-    if any(t.numel() != m for t in img):
-        raise ValueError("huygens_sum: image_x / image_y / image_z differ in size")
+    m = _same_size("huygens_sum", ["image_x", "image_y", "image_z"], img)
     a = torch.as_tensor(amp, device=dev)
     a_im = None
     if a.is_complex():
@@ -1615,9 +1646,7 @@ def huygens_sum(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd_m
     else:
         a = plane(a)
     pup = [plane(v) for v in (pupil_x, pupil_y, pupil_z)] + [a, plane(opd_mm)]
-    n = pup[0].numel()
-    if any(t.numel() != n for t in pup) or (a_im is not None and a_im.numel() != n):
-        raise ValueError("huygens_sum: the pupil arrays differ in size")
+    n = _same_size("huygens_sum", ["pupil_x", "pupil_y", "pupil_z", "amp", "opd_mm"], pup)
     psf = torch.empty(m, dtype=torch.float64, device=dev)
     field = torch.empty(m, dtype=torch.complex128, device=dev) if want_field else None
     pp = (C.c_void_p * 5)(*[t.data_ptr() for t in pup])
@@ -1647,9 +1676,7 @@ def _mtf_arguments(coords, freq, scale, n_bins):
         shape = tuple(getattr(c, "shape", np.shape(c)))
         if len(shape) != 1:
             raise ValueError(f"geometric_mtf: coords[{k}] must be one-dimensional, got {shape}")
-        if isinstance(c, torch.Tensor) and (c.is_complex() or not c.is_floating_point()):
-            raise ValueError(f"geometric_mtf: coords[{k}] must be real floating point, "
-                             f"got {c.dtype}")
+        _real("geometric_mtf", f"coords[{k}]", c)
     fshape = tuple(getattr(freq, "shape", np.shape(freq)))
     if len(fshape) != 1 or fshape[0] < 1:
         raise ValueError(f"geometric_mtf: freq must be a non-empty 1-D array, got shape {fshape}")
@@ -1675,18 +1702,13 @@ def geometric_mtf_launch(coords, freq, scale=None, n_bins=None, *, device=None):
     over as they are (widened on load) when every curve is float32, anything else as float64.
     More than `_capi.MTF_MAX_CURVES` curves go out as several calls."""
     coords, num_points, n_bins = _mtf_arguments(coords, freq, scale, n_bins)
-    lib = _capi.load()
-    if not _capi.has_geometric_mtf(lib):
-        raise _capi.HipExtensionError(
-            f"{_capi.library_path()} has no ol_geometric_mtf; rebuild the library "
-            "(`python -c 'import __graft_entry__ as g; g.build()'`)")
+    lib = _analysis_library(_capi.has_geometric_mtf, "ol_geometric_mtf")
     dev = _require_gpu(device)
     all_f32 = all(isinstance(c, torch.Tensor) and c.dtype == torch.float32 for c in coords)
     dtype = torch.float32 if all_f32 else torch.float64
     planes = [torch.as_tensor(c, device=dev).detach().to(dtype).contiguous() for c in coords]
-    v = torch.as_tensor(freq, device=dev).detach().to(torch.float64).contiguous()
-    s = None if scale is None else \
-        torch.as_tensor(scale, device=dev).detach().to(torch.float64).contiguous()
+    v = _f64_plane(freq, dev)
+    s = None if scale is None else _f64_plane(scale, dev)
     k = len(planes)
     mtf = torch.empty((k, num_points), dtype=torch.float64, device=dev)
     counts = torch.empty((k, n_bins), dtype=torch.int32, device=dev)
@@ -1727,15 +1749,7 @@ def geometric_mtf(coords, freq, scale=None, n_bins=None, want_counts=False, *, d
 
 
 _ZK_TABLES: dict = {}
-
-
-def _zk_library():
-    lib = _capi.load()
-    if not _capi.has_zernike_fit(lib):
-        raise _capi.HipExtensionError(
-            f"{_capi.library_path()} has no ol_zernike_fit / ol_zernike_eval / ol_sampled_mtf; "
-            "rebuild the library (`python -c 'import __graft_entry__ as g; g.build()'`)")
-    return lib
+_ZK_SYMBOLS = "ol_zernike_fit / ol_zernike_eval / ol_sampled_mtf"
 
 
 def _zk_table(kind: str, num_terms: int, dev):
@@ -1749,30 +1763,6 @@ def _zk_table(kind: str, num_terms: int, dev):
         got = (torch.from_numpy(ti.copy()).to(dev), torch.from_numpy(tf.copy()).to(dev))
         _ZK_TABLES[key] = got
     return got
-
-
-def _zk_shape(v):
-    return tuple(v.shape) if hasattr(v, "shape") else tuple(np.shape(v))
-
-
-def _zk_real(who, name, v):
-    if isinstance(v, torch.Tensor) and (v.is_complex() or not v.is_floating_point()):
-        raise ValueError(f"{who}: {name} must be real floating point, got {v.dtype}")
-
-
-def _zk_points(who, names, arrays):
-    """Host-side checks of same-sized real point arrays (nothing here touches a device): n."""
-    sizes = []
-    for name, v in zip(names, arrays):
-        _zk_real(who, name, v)
-        sizes.append(int(np.prod(_zk_shape(v), dtype=np.int64)))
-    if any(s != sizes[0] for s in sizes):
-        raise ValueError(f"{who}: " + " / ".join(names) + f" differ in size ({sizes})")
-    return sizes[0]
-
-
-def _zk_plane(v, dev):
-    return torch.as_tensor(v, device=dev).detach().to(torch.float64).reshape(-1).contiguous()
 
 
 def zernike_fit(x, y, z, kind: str = "fringe", num_terms: int = 37, intensity=None, *,
@@ -1790,10 +1780,10 @@ def zernike_fit(x, y, z, kind: str = "fringe", num_terms: int = 37, intensity=No
     if intensity is not None:
         names.append("intensity")
         arrays.append(intensity)
-    n = _zk_points("zernike_fit", names, arrays)
-    lib = _zk_library()
+    n = _points("zernike_fit", names, arrays)
+    lib = _analysis_library(_capi.has_zernike_fit, _ZK_SYMBOLS)
     dev = _require_gpu(device)
-    planes = [_zk_plane(v, dev) for v in arrays]
+    planes = [_f64_plane(v, dev) for v in arrays]
     ti, tf = _zk_table(kind, num_terms, dev)
     coeffs = torch.empty(num_terms, dtype=torch.float64, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
@@ -1809,8 +1799,8 @@ def zernike_fit(x, y, z, kind: str = "fringe", num_terms: int = 37, intensity=No
 def _zk_coeffs(who, coeffs, kind):
     from . import zernike as Z
 
-    _zk_real(who, "coeffs", coeffs)
-    shape = _zk_shape(coeffs)
+    _real(who, "coeffs", coeffs)
+    shape = _shape(coeffs)
     if len(shape) != 1:
         raise ValueError(f"{who}: coeffs must be one-dimensional, got shape {shape}")
     return Z.check_terms(kind, shape[0], who)
@@ -1820,12 +1810,12 @@ def zernike_eval(coeffs, kind: str, x, y, *, device=None):
     """`ol_zernike_eval`: sum_j coeffs[j] Z_j(x, y) at Cartesian points of any radius (no mask),
     float64, x's shape.  The number of terms is that of `coeffs`."""
     num_terms = _zk_coeffs("zernike_eval", coeffs, kind)
-    n = _zk_points("zernike_eval", ["x", "y"], [x, y])
-    shape = _zk_shape(x)
-    lib = _zk_library()
+    n = _points("zernike_eval", ["x", "y"], [x, y])
+    shape = _shape(x)
+    lib = _analysis_library(_capi.has_zernike_fit, _ZK_SYMBOLS)
     dev = _require_gpu(device)
-    c = _zk_plane(coeffs, dev)
-    px, py = _zk_plane(x, dev), _zk_plane(y, dev)
+    c = _f64_plane(coeffs, dev)
+    px, py = _f64_plane(x, dev), _f64_plane(y, dev)
     ti, tf = _zk_table(kind, num_terms, dev)
     out = torch.empty(n, dtype=torch.float64, device=dev)
     if n:
@@ -1853,26 +1843,26 @@ def sampled_mtf(coeffs, kind: str, x, y, opd_waves, intensity, shifts, *, p1=Non
         arrays.append(opd_waves)
     elif p1 is None:
         raise ValueError("sampled_mtf: neither opd_waves nor p1 is given")
-    n = _zk_points("sampled_mtf", names, arrays)
-    if p1 is not None and int(np.prod(_zk_shape(p1), dtype=np.int64)) != n:
-        raise ValueError(f"sampled_mtf: p1 has {_zk_shape(p1)} entries, x {n}")
-    _zk_real("sampled_mtf", "shifts", shifts)
-    sshape = _zk_shape(shifts)
+    n = _points("sampled_mtf", names, arrays)
+    if p1 is not None and int(np.prod(_shape(p1), dtype=np.int64)) != n:
+        raise ValueError(f"sampled_mtf: p1 has {_shape(p1)} entries, x {n}")
+    _real("sampled_mtf", "shifts", shifts)
+    sshape = _shape(shifts)
     if len(sshape) != 2 or sshape[1] != 2:
         raise ValueError(f"sampled_mtf: shifts must have shape (F, 2), got {sshape}")
     n_freq = int(sshape[0])
     if n_freq > _capi.SMTF_MAX_FREQ:
         raise ValueError(f"sampled_mtf: {n_freq} frequencies, at most {_capi.SMTF_MAX_FREQ}")
-    lib = _zk_library()
+    lib = _analysis_library(_capi.has_zernike_fit, _ZK_SYMBOLS)
     dev = _require_gpu(device)
-    c = _zk_plane(coeffs, dev)
-    planes = [_zk_plane(v, dev) for v in arrays]
+    c = _f64_plane(coeffs, dev)
+    planes = [_f64_plane(v, dev) for v in arrays]
     opd = planes[3] if opd_waves is not None else None
     pupil = None
     if p1 is not None:
         pupil = torch.view_as_real(torch.as_tensor(p1, device=dev).detach().to(torch.complex128)
                                    .reshape(-1).contiguous())
-    sh = torch.as_tensor(shifts, device=dev).detach().to(torch.float64).contiguous()
+    sh = _f64_plane(shifts, dev)  # (dx, dy) pairs
     ti, tf = _zk_table(kind, num_terms, dev)
     mtf = torch.empty(n_freq, dtype=torch.float64, device=dev)
     otf = torch.empty(n_freq, dtype=torch.complex128, device=dev) if want_otf else None

@@ -399,3 +399,62 @@ def test_scalar_pairs():
     assert seams._scalar_pairs([(np.zeros(2), 1.0)]) is None
     assert seams._scalar_pairs([1.0, 2.0]) is None
     assert seams._scalar_pairs(torch.zeros(4)) is None
+
+
+class _OnHip(torch.Tensor):
+    """A host tensor that says it lives on the HIP device (no test here reads its memory)."""
+    device = torch.device("cuda", 0)
+
+
+def _seam_call(seams, oz, key, t):
+    """(public seam function, device function, (self, *args)) of one fp64 analysis seam, every
+    tensor of the call being `t`."""
+    ns = types.SimpleNamespace
+    fit = ns(x=t, y=t, z=t, zernike=oz.ZernikeFringe(t))
+    return {
+        "huygens": (seams._huygens_torch_compute, seams._huygens_device,
+                    (ns(device="cuda"), t, t, t, t, t, t, t, t, 5e-4, 50.0)),
+        "geo_mtf": (seams._geometric_mtf_generate, seams._geometric_mtf_device,
+                    (ns(data=[[ns(x=t, y=t)]], freq=t, num_points=8, scale=False),)),
+        "zfit": (seams._zernike_fit_fit, seams._zernike_fit_device, (fit,)),
+        "smtf": (seams._sampled_mtf_calculate, seams._sampled_mtf_device,
+                 (ns(zernike_fit=fit, P1=t, intensity=t, x_norm=t, y_norm=t, xpd=10.0, xpl=-50.0,
+                     wavelength=0.55), [(0.0, 1.0)])),
+    }[key]
+
+
+@pytest.mark.parametrize("why", ["host tensor", "requires_grad", "grad mode"])
+@pytest.mark.parametrize("key", ["huygens", "geo_mtf", "zfit", "smtf"])
+def test_every_analysis_seam_declines_and_falls_back(stand_ins, monkeypatch, key, why):
+    """Off the HIP device and under autograd (a tensor's own flag, the backend's grad mode) the
+    device function of each of the four seams declines, and the public function then calls the
+    reference's method exactly once and counts one fall-back, nothing else."""
+    seams, be, oz, _fit, _mtf = stand_ins
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(_capi, "load", lambda: object())     # a library that has everything:
+    for has in ("has_huygens", "has_geometric_mtf", "has_zernike_fit"):   # never the reason
+        monkeypatch.setattr(_capi, has, lambda lib: True)
+    grad_mode = types.SimpleNamespace(requires_grad=why == "grad mode")
+    config = types.SimpleNamespace(grad_mode=grad_mode)
+    monkeypatch.setattr(be, "_backends", {"torch": types.SimpleNamespace(_config=config)})
+    t = torch.ones(8, dtype=torch.float64)
+    if why != "host tensor":
+        t = t.as_subclass(_OnHip)
+        assert t.device.type == "cuda"
+    if why == "requires_grad":
+        t.requires_grad_()
+    reasons, calls = [], []
+    monkeypatch.setattr(seams, "_why", lambda seam, reason: reasons.append((seam, reason)))
+    monkeypatch.setitem(seams._ORIG, key, lambda *a: calls.append(a) or "reference")
+    public, device, args = _seam_call(seams, oz, key, t)
+
+    assert device(*args) is None
+    seam, reason = reasons.pop()
+    assert seam == key and not reasons
+    assert ("off the HIP device" if why == "host tensor" else "autograd") in reason
+
+    before = dict(seams.STATS)
+    assert public(*args) == "reference"
+    assert len(calls) == 1 and all(a is b for a, b in zip(calls[0], args))
+    changed = {k: v - before[k] for k, v in seams.STATS.items() if v != before[k]}
+    assert changed == {key + "_fallback": 1}
