@@ -915,6 +915,42 @@ int ol_sampled_mtf(int32_t num_terms, const int32_t* term_i, const double* term_
                    int32_t n_freq, const double* shifts, double* mtf_out, double* otf_out,
                    void* stream);
 
+/* The matrix-multiply DFT of the MMDFT PSF (optiland/psf/mmdft.py:157-201 `_compute_psf` /
+ * `_get_normalization` and :223-283 `_compute_kernels`; R. Soummer et al., Opt. Express 15 (2007)
+ * 15935, the matrix Fourier transform): the PSF on image_size x image_size pixels of any pitch,
+ * straight from the n_side x n_side pupil, without zero padding.  Per pupil g (N = n_side,
+ * M = image_size, integer division in the coordinates):
+ *
+ *   W[v][j]   = exp(-2 pi i (v - M/2) (j - N/2) / pad_size)          (the reference's L; R = W^T)
+ *   G[v][u]   = sum_y W[v][y] sum_x g[y][x] W[u][x]                  (G = L g R)
+ *   psf[v][u] = |G[v][u]|^2 * 100 / c^2,   c = the number of cells with hypot(re, im) > 0
+ *
+ * pupil: n_pupils x N x N complex128 on the DEVICE, row-major, (re, im) interleaved; pad_size:
+ * n_pupils doubles on the HOST, read before the call returns (the reference's pad size,
+ * wavelength * F/# * (N - 1) / pixel_pitch: not an integer in general); psf_out: n_pupils x M x M
+ * doubles on the device; field_out (nullable): G, n_pupils x M x M interleaved (re, im) pairs.
+ * The count is an integer: a NaN cell does not count (as with `abs(pupil) > 0`), and c = 0 gives
+ * 0 * 100 / 0 = NaN in every pixel, as the reference does.  No cell is filtered: every G sums
+ * every cell, so one NaN cell makes every pixel of that pupil NaN; pupils of one call do not
+ * affect each other.  fp64 throughout: (v - M/2) (j - N/2) is an exact integer, the phase is
+ * carried in cycles as the quotient AND the remainder of the division by pad_size and reduced
+ * exactly, so a table entry is good to 3 ulp whatever the size of the phase; the two products
+ * are tiled fp64 FMA kernels whose reductions run in index order in one accumulator per output,
+ * no floating-point atomics: bit-identical from run to run, and a pupil's result does not depend
+ * on the others of the call.  Four launches per 32 pupils on `stream`; stream-ordered workspace
+ * (hipMallocAsync): 32 M N bytes per pupil of a slice of at most 32.
+ * OL_MMDFT_MAX_SIDE bounds n_side and image_size: |(v - M/2) (j - N/2)| <= 2^24 then fits an
+ * int32 and is exact in fp64, c^2 <= 2^52 is exact, M N and M^2 <= 2^26 entries, and the
+ * workspace (at most 32 pupils x 2^26 entries x 32 bytes) is far inside size_t.
+ * OL_EINVAL (decided before any device call): negative n_pupils, n_side or image_size outside
+ * 1..OL_MMDFT_MAX_SIDE, NULL pupil / pad_size / psf_out, a pad_size entry that is not finite and
+ * > 0 (the message names its index).  image_size > pad_size is NOT refused here (the transform
+ * is well defined, its image merely wraps); the Python layers raise the reference's ValueError.
+ * n_pupils = 0 is a no-op.                                                                   */
+#define OL_MMDFT_MAX_SIDE 8192
+int ol_mmdft_psf(int32_t n_pupils, int32_t n_side, const double* pupil, const double* pad_size,
+                 int32_t image_size, double* psf_out, double* field_out, void* stream);
+
 /* Profiling knobs (process-wide, not part of the trace semantics).
  *   OL_TUNE_RAYS_PER_THREAD  0 = auto (16-byte vector of rays per lane for conic-only
  *                            ranges, one ray per lane when Newton surfaces are

@@ -149,6 +149,7 @@ EXPORTS = (
     "ol_zernike_fit",
     "ol_zernike_eval",
     "ol_sampled_mtf",
+    "ol_mmdft_psf",
 )
 
 F32, F64 = 0, 1
@@ -296,6 +297,9 @@ def bind(lib, path: str = "?"):
         lib.ol_sampled_mtf.restype = C.c_int
         lib.ol_sampled_mtf.argtypes = [i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp,
                                        vp]
+    if has_mmdft(lib):   # (additive within ABI 11, like ol_huygens_psf)
+        lib.ol_mmdft_psf.restype = C.c_int
+        lib.ol_mmdft_psf.argtypes = [i32, i32, vp, C.POINTER(C.c_double), i32, vp, vp, vp]
     return lib
 
 
@@ -315,6 +319,14 @@ MTF_MAX_CURVES, MTF_MAX_BINS, MTF_NONFINITE = 64, 8192, 1   # OL_MTF_* (optiland
 def has_geometric_mtf(lib) -> bool:
     """True when the loaded library exports ol_geometric_mtf."""
     return hasattr(lib, "ol_geometric_mtf")
+
+
+MMDFT_MAX_SIDE = 8192   # OL_MMDFT_MAX_SIDE (optiland_hip.h)
+
+
+def has_mmdft(lib) -> bool:
+    """True when the loaded library exports ol_mmdft_psf."""
+    return hasattr(lib, "ol_mmdft_psf")
 
 
 def has_huygens(lib) -> bool:

@@ -59,7 +59,8 @@ STATS = {"spot": 0, "spot_fallback": 0, "ee": 0, "ee_fallback": 0, "opd": 0, "op
          "pupil": 0, "pupil_fallback": 0, "opd_init": 0, "opd_init_fallback": 0,
          "dist": 0, "dist_fallback": 0, "opd_fit": 0, "opd_fit_fallback": 0, "spot_grid": 0,
          "spot_radius": 0, "huygens": 0, "huygens_fallback": 0, "geo_mtf": 0,
-         "geo_mtf_fallback": 0, "zfit": 0, "zfit_fallback": 0, "smtf": 0, "smtf_fallback": 0}
+         "geo_mtf_fallback": 0, "zfit": 0, "zfit_fallback": 0, "smtf": 0, "smtf_fallback": 0,
+         "mmdft": 0, "mmdft_fallback": 0}
 
 
 def _why(seam, reason):
@@ -1162,7 +1163,7 @@ def _uniform_generate_points(self, num_points):
 
 
 # --------------------------------------------------------------------------- fp64 analysis kernels
-# (Huygens PSF, geometric MTF, Zernike fit, sampled MTF: what their four seams share)
+# (Huygens PSF, geometric MTF, Zernike fit, sampled MTF, MMDFT PSF: what their seams share)
 def _grad_mode(be) -> bool:
     try:
         return bool(be._backends[be.get_backend()]._config.grad_mode.requires_grad)
@@ -1451,6 +1452,89 @@ def _sampled_mtf_device(self, frequencies):
     return list(mtf.to(real))
 
 
+# --------------------------------------------------------------------------- MMDFT PSF
+# num_rays x image_size^2 above which the seam leaves the product to the reference: measured
+# (profiles/mmdft.txt), the whole `ol_mmdft_psf` call beat the reference's torch route at
+# (64, 512) and below on both visits; at (181, 2048) its per-call workspace allocation made it
+# the slower one on one visit of two (0.44 against 0.31 ms; 0.23 on the other)
+_MMDFT_MAX_WORK = 64 * 512 * 512
+
+
+def _mmdft_compute_psf(self):
+    """psf/mmdft.py:157-177 (`MMDFTPSF._compute_psf`) with `ol_mmdft_psf`: one twiddle table from
+    an exactly reduced phase, the two products G = L g R as tiled fp64 kernels and the scaled
+    |G|^2 as the second one's epilogue, instead of ten elementwise launches for L and R and two
+    complex128 `matmul`s.  Same shape as the reference, in the backend's real precision (a
+    float32 backend gets the fp64 result cast down).  Raises the reference's ValueError for an
+    `image_size` beyond the pad size.  Falls back to the reference's method off the HIP device,
+    under autograd, with a library that lacks the kernel, for a pupil that is not a square
+    complex device tensor, for a subclass that overrides `_compute_kernels` or
+    `_get_normalization` (it keeps its own code), and above `_MMDFT_MAX_WORK`, where the
+    reference's route was measured to be the faster one."""
+    return _served("mmdft", _mmdft_device(self), self)
+
+
+def _mmdft_device(self):
+    import optiland.backend as be
+
+    from . import _capi
+
+    # (the library first: without the kernel nothing else matters)
+    if not (_torch_on_hip("mmdft", be)
+            and _device_ready("mmdft", [], _capi.has_mmdft, "ol_mmdft_psf")):
+        return None
+    # the class this seam sits on, and whether what `self` resolves the two helpers to is
+    # still what that class defines
+    cls = type(self)
+    base = next((c for c in cls.__mro__ if c.__dict__.get("_compute_psf") is _mmdft_compute_psf),
+                None)
+    if base is None or any(getattr(cls, name, None) is not base.__dict__.get(name)
+                           for name in ("_compute_kernels", "_get_normalization")):
+        _why("mmdft", f"{cls.__name__} overrides _compute_kernels or _get_normalization")
+        return None
+    pupil = getattr(self, "pupil", None)
+    if not isinstance(pupil, torch.Tensor) or not pupil.is_complex() or pupil.ndim != 2 \
+            or pupil.shape[0] != pupil.shape[1] or pupil.shape[0] != self.num_rays:
+        _why("mmdft", "the pupil is not a square complex tensor of num_rays")
+        return None
+    if pupil.device.type != "cuda":
+        _why("mmdft", "the pupil lives off the HIP device")
+        return None
+    if pupil.requires_grad:
+        _why("mmdft", "autograd")
+        return None
+    image_size = self.image_size
+    if isinstance(image_size, bool) or not isinstance(image_size, int) \
+            or not 1 <= image_size <= _capi.MMDFT_MAX_SIDE \
+            or not 1 <= pupil.shape[0] <= _capi.MMDFT_MAX_SIDE:
+        _why("mmdft", f"image_size {image_size!r}, num_rays {pupil.shape[0]}")
+        return None
+    if pupil.shape[0] * image_size * image_size > _MMDFT_MAX_WORK:
+        _why("mmdft", f"num_rays {pupil.shape[0]} x image_size {image_size}^2 is above the "
+                      "measured crossover")
+        return None
+    # mmdft.py:239-254, the same expression in the same order
+    clear_size = self.num_rays - 1
+    pad_size = (self.wavelengths[0].value * self._get_working_FNO() * clear_size
+                / self.pixel_pitch)
+    if isinstance(pad_size, torch.Tensor) and pad_size.requires_grad:
+        _why("mmdft", "autograd")
+        return None
+    if image_size > pad_size:
+        max_size = int(pad_size)
+        raise ValueError(f"Supplied image_size of {image_size} not less than or equal to "
+                         f"calculated pad size of {max_size}. Consider increasing num_rays.")
+    pad = _f(pad_size)
+    if not (math.isfinite(pad) and pad > 0):
+        _why("mmdft", f"pad size {pad}")
+        return None
+    from .engine import mmdft_psf
+
+    psf = mmdft_psf(pupil.detach(), pad, image_size, device=pupil.device)
+    real = torch.float32 if be.get_complex_precision() == torch.complex64 else torch.float64
+    return psf.to(real)
+
+
 # --------------------------------------------------------------------------- (de)activate
 # The seams replace PRIVATE methods of the reference.  Each entry: key in _ORIG -> (module,
 # class, method, the parameter names the replacement was written against, replacement).  A
@@ -1502,6 +1586,7 @@ _SEAMS = {
     "zfit": ("optiland.zernike.fit", "ZernikeFit", "_fit", ("self",), "_zernike_fit_fit"),
     "smtf": ("optiland.mtf.sampled", "SampledMTF", "calculate_mtf", ("self", "frequencies"),
              "_sampled_mtf_calculate"),
+    "mmdft": ("optiland.psf.mmdft", "MMDFTPSF", "_compute_psf", ("self",), "_mmdft_compute_psf"),
 }
 def _constructor_scope(key):
     """A constructor of the reference that only READS its optic -- `Wavefront.__init__`

@@ -1578,6 +1578,10 @@ class HipSystem:
         """`huygens_sum` (module level) on this system's device."""
         return huygens_sum(*args, device=self.device, **kwargs)
 
+    def mmdft_psf(self, *args, **kwargs):
+        """`mmdft_psf` (module level) on this system's device."""
+        return mmdft_psf(*args, device=self.device, **kwargs)
+
 
 def _analysis_library(has, symbols: str):
     """The loaded library if `has` finds its entry points in it, else the way to get them."""
@@ -1659,6 +1663,65 @@ def huygens_sum(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd_m
     _capi.check(rc, "ol_huygens_psf", lib)
     psf = psf.reshape(shape)
     return (psf, field.reshape(shape)) if want_field else psf
+
+
+def _mmdft_arguments(pupil, pad_size, image_size):
+    """The host-side checks of `mmdft_psf` (nothing here touches a device): (batched, B, N, M,
+    the pad sizes as a list of B floats)."""
+    shape = _shape(pupil)
+    if len(shape) not in (2, 3) or shape[-1] != shape[-2]:
+        raise ValueError(f"mmdft_psf: pupil must have shape (N, N) or (B, N, N), got {shape}")
+    dtype = str(pupil.dtype if hasattr(pupil, "dtype") else np.asarray(pupil).dtype)
+    if "complex" not in dtype:
+        raise ValueError(f"mmdft_psf: pupil must be complex, got {dtype}")
+    batched = len(shape) == 3
+    b, n = (shape[0] if batched else 1), shape[-1]
+    if isinstance(image_size, bool) or int(image_size) != image_size:
+        raise ValueError(f"mmdft_psf: image_size must be an integer, got {image_size!r}")
+    m = int(image_size)
+    for name, v in (("the pupil's side", n), ("image_size", m)):
+        if not 1 <= v <= _capi.MMDFT_MAX_SIDE:
+            raise ValueError(f"mmdft_psf: {name} {v} is outside 1..{_capi.MMDFT_MAX_SIDE}")
+    if isinstance(pad_size, torch.Tensor):
+        pad_size = pad_size.detach().cpu().numpy()
+    pads = np.asarray(pad_size, dtype=np.float64)
+    if pads.ndim == 0:   # one float: every pupil's
+        pads = np.full(b, float(pads))
+    if pads.shape != (b,):
+        raise ValueError(f"mmdft_psf: pad_size must be a float or {b} floats, got shape "
+                         f"{pads.shape}")
+    for k, v in enumerate(pads.tolist()):
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"mmdft_psf: pad_size[{k}] = {v} must be finite and positive")
+    return batched, b, n, m, pads.tolist()
+
+
+def mmdft_psf(pupil, pad_size, image_size: int, *, want_field: bool = False, device=None):
+    """`ol_mmdft_psf`: the matrix-multiply DFT of psf/mmdft.py:157-283 on the device, fp64
+    throughout (a complex64 pupil is widened).
+
+    pupil: (N, N) or (B, N, N) complex tensor or array; pad_size: a float, or B floats for a
+    batch (the reference's wavelength * F/# * (N - 1) / pixel_pitch); image_size: M.  Returns
+    psf = |G|^2 * 100 / c^2, c the number of cells with |g| > 0 (float64, (M, M) or (B, M, M)),
+    or with `want_field` (psf, G) with G complex128.  `image_size > pad_size` is the caller's to
+    refuse (`wavefront.MMDFTPSF` and the drop-in raise the reference's ValueError).  Tensors on
+    another device are copied to `device` (default: the current HIP device)."""
+    batched, b, n, m, pads = _mmdft_arguments(pupil, pad_size, image_size)
+    lib = _analysis_library(_capi.has_mmdft, "ol_mmdft_psf")
+    dev = _require_gpu(device)
+    g = torch.view_as_real(torch.as_tensor(pupil, device=dev).detach().to(torch.complex128)
+                           .reshape(b, n, n).contiguous())
+    psf = torch.empty((b, m, m), dtype=torch.float64, device=dev)
+    field = torch.empty((b, m, m), dtype=torch.complex128, device=dev) if want_field else None
+    if b:
+        with torch.cuda.device(dev):
+            rc = lib.ol_mmdft_psf(b, n, g.data_ptr(), (C.c_double * b)(*pads), m, psf.data_ptr(),
+                                  field.data_ptr() if field is not None else None,
+                                  _stream_ptr(dev))
+        _capi.check(rc, "ol_mmdft_psf", lib)
+    if not batched:
+        psf, field = psf[0], (field[0] if field is not None else None)
+    return (psf, field) if want_field else psf
 
 
 def _mtf_arguments(coords, freq, scale, n_bins):

@@ -346,6 +346,31 @@ def calculate_grid_size(num_rays: int) -> tuple[int, int]:
     return eff, num_rays * 2
 
 
+def padded_pupil(wavefront, n: int, gsz: int) -> torch.Tensor:
+    """The pupil function of a uniform-grid `wavefront` of n x n samples (psf/fft.py:101-137,
+    copied by psf/mmdft.py:121-155): A exp(-i 2 pi OPD) on the disc, 0 off it, centred in a
+    zeroed gsz x gsz complex128 grid (gsz = n: the pupil itself)."""
+    d = wavefront.data
+    # the disc mask comes from the SAME arithmetic that placed the traced samples
+    # (distribution._uniform: np.linspace + np.meshgrid, row-major ravel) -- a
+    # torch.linspace grid differs by an ulp on boundary points such as (0.6, 0.8)
+    # and would select a different number of cells for many odd n
+    g = np.linspace(-1.0, 1.0, n)
+    xg, yg = np.meshgrid(g, g)
+    cells = np.flatnonzero((xg**2 + yg**2 <= 1).reshape(-1)).astype(np.int32)
+    before = (gsz - n) // 2
+    eng = wavefront.tracer.engine
+    if wavefront.fused and hasattr(eng, "pupil_fill"):
+        cell = torch.from_numpy(cells).to(d.opd.device)
+        return eng.pupil_fill(d.opd, d.intensity, cell, n, gsz)
+    # un-fused path (polarised systems, other strategies, A/B): plain tensor ops
+    P = torch.zeros(n * n, dtype=torch.complex128, device=d.opd.device)
+    P[torch.from_numpy(cells.astype(np.int64)).to(d.opd.device)] = \
+        torch.sqrt(d.intensity) * torch.exp(-2j * math.pi * d.opd)
+    after = before + (gsz - n) % 2
+    return torch.nn.functional.pad(P.reshape(n, n), (before, after, before, after))
+
+
 class FFTPSF:
     """Scalar FFT PSF (psf/fft.py:42-262) for one field and wavelength."""
 
@@ -368,26 +393,8 @@ class FFTPSF:
         """psf/fft.py:101-137: A exp(-i 2 pi OPD) on the num_rays^2 grid, 0 off-disc --
         written straight into the zero-padded FFT grid by `ol_pupil_fill` (self._padded);
         the n x n block is returned as a view."""
-        d = self.wavefront.data
-        n, gsz = self.num_rays, self.grid_size
-        # the disc mask comes from the SAME arithmetic that placed the traced samples
-        # (distribution._uniform: np.linspace + np.meshgrid, row-major ravel) -- a
-        # torch.linspace grid differs by an ulp on boundary points such as (0.6, 0.8)
-        # and would select a different number of cells for many odd n
-        g = np.linspace(-1.0, 1.0, n)
-        xg, yg = np.meshgrid(g, g)
-        cells = np.flatnonzero((xg**2 + yg**2 <= 1).reshape(-1)).astype(np.int32)
-        before = (gsz - n) // 2
-        eng = self.wavefront.tracer.engine
-        if self.wavefront.fused and hasattr(eng, "pupil_fill"):
-            cell = torch.from_numpy(cells).to(d.opd.device)
-            self._padded = eng.pupil_fill(d.opd, d.intensity, cell, n, gsz)
-        else:  # un-fused path (polarised systems, other strategies, A/B): plain tensor ops
-            P = torch.zeros(n * n, dtype=torch.complex128, device=d.opd.device)
-            P[torch.from_numpy(cells.astype(np.int64)).to(d.opd.device)] = \
-                torch.sqrt(d.intensity) * torch.exp(-2j * math.pi * d.opd)
-            after = before + (gsz - n) % 2
-            self._padded = torch.nn.functional.pad(P.reshape(n, n), (before, after, before, after))
+        n, before = self.num_rays, (self.grid_size - self.num_rays) // 2
+        self._padded = padded_pupil(self.wavefront, n, self.grid_size)
         return self._padded[before:before + n, before:before + n]
 
     def _compute_psf(self) -> torch.Tensor:
@@ -423,6 +430,62 @@ def working_fno(t, field, wavelength) -> float:
     if math.isnan(fno):
         raise ValueError("Working F/# could not be calculated due to raytrace errors.")
     return fno
+
+
+class MMDFTPSF:
+    """Matrix-multiply DFT PSF (psf/mmdft.py:19-283) for one field and wavelength: the PSF on
+    `image_size` x `image_size` pixels of `pixel_pitch` um, straight from the num_rays^2 pupil of
+    the device wavefront (no zero padding), by `ol_mmdft_psf`; a diffraction-limited system
+    peaks at 100."""
+
+    def __init__(self, tracer, field, wavelength, num_rays: int = 128, image_size=None,
+                 pixel_pitch=None, strategy: str = "chief_ray", remove_tilt: bool = False,
+                 **kwargs):
+        # mmdft.py:72-118, to the letter
+        if image_size is None and pixel_pitch is None:
+            if num_rays < 32:
+                raise ValueError("num_rays must be at least 32 if image_size and pixel_pitch are "
+                                 "not specified.")
+            num_rays, grid_size = calculate_grid_size(num_rays)
+        self.tracer, self.num_rays = tracer, num_rays
+        self.wavefront = Wavefront(tracer, field, wavelength, num_rays, "uniform",
+                                   strategy=strategy, remove_tilt=remove_tilt, **kwargs)
+        self.field, self.wavelength = self.wavefront.field, self.wavefront.wavelength
+        clear_size = num_rays - 1
+        if pixel_pitch is None:
+            if image_size is None:
+                image_size = grid_size
+            pixel_pitch = self.wavelength * self.working_fno() * clear_size / image_size
+        if image_size is None:   # the largest image of that pitch: the pad size, truncated
+            image_size = int(self.wavelength * self.working_fno() * clear_size / pixel_pitch)
+        self.image_size, self.pixel_pitch = image_size, pixel_pitch
+        self.pupil = padded_pupil(self.wavefront, num_rays, num_rays)
+        self.psf = self._compute_psf()
+
+    def working_fno(self) -> float:
+        """utils.py:45-106 get_working_FNO: chief ray + four marginal rays."""
+        return working_fno(self.tracer, self.field, self.wavelength)
+
+    def pad_size(self) -> float:
+        """mmdft.py:239-245: the side of the zero-padded grid an FFT of this pitch would need."""
+        return self.wavelength * self.working_fno() * (self.num_rays - 1) / self.pixel_pitch
+
+    def _product(self, pupil, pad_size, image_size):
+        from .engine import mmdft_psf
+        return mmdft_psf(pupil, pad_size, image_size, device=pupil.device)
+
+    def _compute_psf(self) -> torch.Tensor:
+        """mmdft.py:157-177 and the check of :247-254."""
+        pad_size = self.pad_size()
+        if self.image_size > pad_size:
+            raise ValueError(f"Supplied image_size of {self.image_size} not less than or equal to "
+                             f"calculated pad size of {int(pad_size)}. Consider increasing "
+                             "num_rays.")
+        return self._product(self.pupil, pad_size, self.image_size)
+
+    def strehl_ratio(self) -> float:
+        """mmdft.py:203-221: the maximum (the PSF need not be centred in the image)."""
+        return float(self.psf.max()) / 100
 
 
 class HuygensPSF:
