@@ -951,6 +951,49 @@ int ol_sampled_mtf(int32_t num_terms, const int32_t* term_i, const double* term_
 int ol_mmdft_psf(int32_t n_pupils, int32_t n_side, const double* pupil, const double* pad_size,
                  int32_t image_size, double* psf_out, double* field_out, void* stream);
 
+/* Iterative ray aiming (additive within ABI 11; rays/ray_aiming/iterative.py:60-281,
+ * `IterativeRayAimer.aim_rays`): for every ray, the launch coordinates whose trace through
+ * surfaces [first_surface, stop_surface] lands on (px r_stop, py r_stop) in the stop surface's
+ * own frame -- a Newton iteration on a 2 x 2 Jacobian estimate that starts as
+ * diag(jacobian, jacobian) (|jacobian| < 1e-12 -> 1e-12) and takes a Broyden rank-1 update per
+ * step, at most max_iter steps, until ex^2 + ey^2 < tol^2.  The unknowns are (x, y) for an
+ * object at infinity (`infinite`) and (L, M) otherwise; N is not renormalised, as in the
+ * reference (trace such bundles with OL_TRACE_NONUNIT_K where it matters).  ONE kernel, one ray
+ * per lane, fp64 only; the rays of a call do not affect each other.
+ *   start     `guess` != NULL: six device planes x, y, z, L, M, N (the reference's
+ *             `initial_guess`; `in` then only supplies px, py).  Else the paraxial launch state
+ *             of (hx, hy, px, py, vx, vy) -- `in` as for ol_generate_rays, `p->raygen` the
+ *             generator's scalars -- formed by the function the generating kernels use.
+ *   out       six device planes of n_rays doubles (may alias `guess`)
+ *   updates   nullable device int32 plane: the number of steps that moved each ray
+ *   status    device uint32, required; bits are OR-ed in: OL_STATUS_* of the surfaces traced,
+ *             OL_AIM_NAN_GUESS when a ray's FIRST error is NaN (the reference raises "Initial ray
+ *             aiming guess produced NaNs. ..."), OL_AIM_NOT_CONVERGED when a ray ends with
+ *             ex^2 + ey^2 < tol^2 false, NaN included ("Iterative aimer failed to converge.").
+ *             The reference decides both for the batch: so does the caller, from this word.
+ * OL_EINVAL (before any device call): NULL sys / p / in / in->px / in->py / out / out[k] /
+ * guess[k] / status, hx / hy or vx / vy not given together, negative n_rays, a wavelength index
+ * or a surface range outside the table, max_iter outside [0, OL_AIM_MAX_ITER], tol negative or
+ * not finite, r_stop or jacobian NaN, the wrong current device.  OL_EUNSUPPORTED: a surface of
+ * the range carries OL_SURF_REFERENCE_NEWTON (its iteration count is a property of the batch, not
+ * of a ray).  Coatings do not enter: the solve reads positions only.  n_rays = 0 is a no-op
+ * once the arguments have passed.                                                            */
+#define OL_AIM_NAN_GUESS 0x100u
+#define OL_AIM_NOT_CONVERGED 0x200u
+#define OL_AIM_MAX_ITER 1000
+typedef struct ol_aim_params {
+  double stop_radius;  /* r_stop: the target is (px, py) * stop_radius                     */
+  double jacobian;     /* paraxial d(stop height) / d(unknown), `_get_paraxial_jacobian`   */
+  double tol;          /* convergence: ex^2 + ey^2 < tol^2                                 */
+  int32_t max_iter;    /* 0 ... OL_AIM_MAX_ITER                                            */
+  int32_t infinite;    /* object at infinity: solve for (x, y); else for (L, M)            */
+  ol_raygen_params raygen; /* read only when `guess` is NULL                               */
+} ol_aim_params;
+int ol_aim_rays(const ol_system* sys, int64_t n_rays, int32_t wavelength_index,
+                int32_t first_surface, int32_t stop_surface, const ol_aim_params* p,
+                const ol_raygen_inputs* in, const void* const guess[6], void* const out[6],
+                int32_t* updates, uint32_t* status, void* stream);
+
 /* Profiling knobs (process-wide, not part of the trace semantics).
  *   OL_TUNE_RAYS_PER_THREAD  0 = auto (16-byte vector of rays per lane for conic-only
  *                            ranges, one ray per lane when Newton surfaces are

@@ -150,6 +150,7 @@ EXPORTS = (
     "ol_zernike_eval",
     "ol_sampled_mtf",
     "ol_mmdft_psf",
+    "ol_aim_rays",
 )
 
 F32, F64 = 0, 1
@@ -300,6 +301,10 @@ def bind(lib, path: str = "?"):
     if has_mmdft(lib):   # (additive within ABI 11, like ol_huygens_psf)
         lib.ol_mmdft_psf.restype = C.c_int
         lib.ol_mmdft_psf.argtypes = [i32, i32, vp, C.POINTER(C.c_double), i32, vp, vp, vp]
+    if has_aim_rays(lib):   # (additive within ABI 11, like ol_huygens_psf)
+        lib.ol_aim_rays.restype = C.c_int
+        lib.ol_aim_rays.argtypes = [vp, i64, i32, i32, i32, vp, vp, C.POINTER(vp), C.POINTER(vp),
+                                    vp, vp, vp]
     return lib
 
 
@@ -327,6 +332,20 @@ MMDFT_MAX_SIDE = 8192   # OL_MMDFT_MAX_SIDE (optiland_hip.h)
 def has_mmdft(lib) -> bool:
     """True when the loaded library exports ol_mmdft_psf."""
     return hasattr(lib, "ol_mmdft_psf")
+
+
+AIM_NAN_GUESS, AIM_NOT_CONVERGED, AIM_MAX_ITER = 0x100, 0x200, 1000   # OL_AIM_* (optiland_hip.h)
+
+
+class AimParams(C.Structure):
+    """ol_aim_params"""
+    _fields_ = [("stop_radius", C.c_double), ("jacobian", C.c_double), ("tol", C.c_double),
+                ("max_iter", C.c_int32), ("infinite", C.c_int32), ("raygen", RaygenParams)]
+
+
+def has_aim_rays(lib) -> bool:
+    """True when the loaded library exports ol_aim_rays."""
+    return hasattr(lib, "ol_aim_rays")
 
 
 def has_huygens(lib) -> bool:

@@ -30,7 +30,10 @@ for exactly that:
   Cholesky and one refinement step in five kernels instead of a few thousand tiny launches
   before `lstsq` (`ZernikeOPD` and `SampledMTF` fit through it);
 * `SampledMTF.calculate_mtf` (mtf/sampled.py:108-207) -> `ol_sampled_mtf`: every frequency of
-  the call in two kernels (`MTFVsField`, `ThroughFocusMTF` are built on it).
+  the call in two kernels (`MTFVsField`, `ThroughFocusMTF` are built on it);
+* `IterativeRayAimer.aim_rays` (rays/ray_aiming/iterative.py:60-281) -> `ol_aim_rays`: the Broyden
+  solve of "iterative" ray aiming -- and, through `RobustRayAimer._iterative`, of "robust" -- in
+  one launch instead of up to max_iter surface-by-surface traces of the batch.
 
 Every patched method first asks whether the call is one the fused path covers -- drop-in
 active for this optic, torch backend on the HIP device without autograd, a system the
@@ -60,7 +63,7 @@ STATS = {"spot": 0, "spot_fallback": 0, "ee": 0, "ee_fallback": 0, "opd": 0, "op
          "dist": 0, "dist_fallback": 0, "opd_fit": 0, "opd_fit_fallback": 0, "spot_grid": 0,
          "spot_radius": 0, "huygens": 0, "huygens_fallback": 0, "geo_mtf": 0,
          "geo_mtf_fallback": 0, "zfit": 0, "zfit_fallback": 0, "smtf": 0, "smtf_fallback": 0,
-         "mmdft": 0, "mmdft_fallback": 0}
+         "mmdft": 0, "mmdft_fallback": 0, "aim": 0, "aim_fallback": 0}
 
 
 def _why(seam, reason):
@@ -1535,6 +1538,194 @@ def _mmdft_device(self):
     return psf.to(real)
 
 
+# --------------------------------------------------------------------------- iterative ray aiming
+def _iterative_aim_rays(self, fields, wavelengths, pupil_coords, initial_guess=None):
+    """rays/ray_aiming/iterative.py:60-281 (`IterativeRayAimer.aim_rays`) with `ol_aim_rays`: the
+    whole Broyden solve -- up to max_iter traces of the batch from the object to the stop, surface
+    by surface, with a host decision after each -- as ONE launch, one ray per lane, and one
+    read-back of a status word from which the reference's two ValueErrors are raised.
+    `RobustRayAimer` reaches it through its `_iterative` member, with an `initial_guess`.  Without
+    one the paraxial launch state is formed in the kernel (the reference's paraxial aimer asks
+    for EPL and EPD, two paraxial traces, per call).  The stop radius, the paraxial Jacobian and
+    the generator's scalars are remembered per optic under the drop-in's change token.  Falls
+    back to the reference's method when the drop-in does not serve the optic (backend, device,
+    autograd, a system the packer refuses), off fp64, for per-ray wavelengths, reference-rule
+    Newton surfaces in front of the stop, inputs that are not arrays of one length on the
+    device, or an engine without the entry point.  `STATS["aim"]` counts the solves launched,
+    those that end in one of the two ValueErrors included."""
+    args = (fields, wavelengths, pupil_coords, initial_guess)
+    out = _aim_device(self, *args)
+    if out is None:
+        STATS["aim_fallback"] += 1
+        return _ORIG["aim"](self, *args)
+    return out
+
+
+def _aim_planes(values, dev):
+    """The arguments as fp64 planes of one length on `dev` (the reference's `as_array_1d` and
+    its broadcasting of one-element arrays), or None."""
+    planes = []
+    for v in values:
+        if isinstance(v, torch.Tensor):
+            if v.requires_grad or (v.device.type != dev.type and v.numel() > 1):
+                return None
+            planes.append(v.detach().to(device=dev, dtype=torch.float64).reshape(-1))
+        else:
+            try:
+                a = np.atleast_1d(np.asarray(v, dtype=np.float64)).reshape(-1)
+            except (TypeError, ValueError):
+                return None
+            planes.append(torch.as_tensor(a, device=dev))
+    n = max(int(p.numel()) for p in planes)
+    if any(p.numel() not in (1, n) for p in planes):
+        return None
+    return [(p.expand(n) if p.numel() != n else p).contiguous() for p in planes]
+
+
+def _aim_stop_radius(self, comp, stop, infinite):
+    """What `get_stop_radius_strategy(optic, "iterative").calculate_stop_radius()` returns
+    (rays/ray_aiming/initialization.py).  `RealReferenceStrategy`'s marginal ray (:89-167) is one
+    ray through surfaces [1, stop] on the device (`ol_trace`) instead of the reference's surface
+    loop; a NaN takes the reference's own way out, warning included."""
+    import warnings
+
+    from optiland.rays.ray_aiming import initialization as init
+
+    optic = self.optic
+    strategy = init.get_stop_radius_strategy(optic, "iterative")
+    if type(strategy) is not init.RealReferenceStrategy:
+        return float(strategy.calculate_stop_radius())   # (no trace in the other two)
+    try:
+        w = _f(optic.primary_wavelength)
+        eng, table, _fronts = comp._entry_for(w)
+        rg_epl, rg_epd = float(optic.paraxial.EPL()), float(optic.paraxial.EPD())
+        if infinite:   # :103-120
+            start = [0.0, rg_epd / 2.0, _f(optic.surfaces[1].geometry.cs.z) - 100.0,
+                     0.0, 0.0, 1.0]
+        else:          # :122-148
+            obj_z = _f(optic.object_surface.geometry.cs.z)
+            dy, dz = rg_epd / 2.0, rg_epl - obj_z
+            mag = math.sqrt(dy * dy + dz * dz)
+            start = [0.0, 0.0, obj_z, 0.0, dy / mag, dz / mag]
+        rays = torch.tensor(start + [1.0, 0.0], dtype=torch.float64,
+                            device=eng.device).reshape(8, 1)
+        eng.trace([rays[k] for k in range(8)], table.wavelength_index(w), record=False, first=1,
+                  last=stop, write_rays=True)
+        g = rays[:3, 0].cpu().numpy()
+        if np.isnan(g[0]):
+            raise ValueError("Ray trace resulted in NaNs (TIR or missed surface).")
+        row = table.surfaces[stop]
+        local = np.asarray(row["rot"], dtype=np.float64).reshape(3, 3) @ \
+            (g - np.asarray(row["origin"], dtype=np.float64))
+        return float(math.hypot(local[0], local[1]))
+    except Exception as exc:  # noqa: BLE001 - initialization.py:81-88, the same way out
+        warnings.warn(f"RealReferenceStrategy failed: {exc}. "
+                      "Falling back to ParaxialReferenceStrategy.", stacklevel=2)
+        return float(init.ParaxialReferenceStrategy(optic).calculate_stop_radius())
+
+
+def _aim_scalars(self, comp, table, w, stop, infinite):
+    """(r_stop, J_factor, raygen, fields) of this optic at wavelength `w` -- the last two the
+    scalars of the paraxial start (`packer.paraxial_start_scalars`) -- remembered on the drop-in's
+    tracer under the change token of the table they were computed for, so that an aim call -- the
+    robust aimer makes tens per trace -- pays neither a paraxial trace nor the marginal ray."""
+    from . import packer
+
+    memo = comp._hip_memo.get(w)
+    tok = memo[0] if memo is not None else None
+    store = comp.__dict__.setdefault("_hip_aim_memo", {})
+    hit = store.get(w)
+    if tok is not None and hit is not None and hit[0] == (tok, stop):
+        return hit[1]
+    # iterative.py:151-156, 283-307 (the wavelength is a scalar here: its own mean)
+    got = (_aim_stop_radius(self, comp, stop, infinite),
+           _f(self._get_paraxial_jacobian(float(w), stop, infinite)),
+           *packer.paraxial_start_scalars(self.optic, table))
+    if tok is not None:
+        # (the marginal ray may have packed the primary wavelength: that does not move w's token)
+        store[w] = ((tok, stop), got)
+        while len(store) > 8:
+            store.pop(next(iter(store)))
+    return got
+
+
+def _aim_device(self, fields, wavelengths, pupil_coords, initial_guess):
+    import optiland.backend as be
+
+    from . import integration as ig
+    from . import packer
+
+    optic = self.optic
+    comp = ig.hip_tracer_of(optic)
+    if comp is None or not comp._eligible():
+        _why("aim", "optic not served by the drop-in (backend / device / autograd)")
+        return None
+    if comp._dtype() != torch.float64:
+        _why("aim", "not an fp64 backend")
+        return None
+    w = _scalar(wavelengths)
+    if w is None and isinstance(wavelengths, torch.Tensor) and wavelengths.numel() > 1 \
+            and not wavelengths.requires_grad:
+        lo, hi = torch.aminmax(wavelengths.detach())
+        w = float(lo) if float(lo) == float(hi) else None
+    if w is None:
+        _why("aim", "per-ray wavelengths")
+        return None
+    try:
+        eng, table, _fronts = comp._entry_for(w)
+    except UnsupportedSystem as exc:
+        _why("aim", f"unsupported system: {exc}")
+        return None
+    can = getattr(eng, "can_aim_rays", None)
+    if can is None or not can():
+        _why("aim", "an engine without ol_aim_rays")
+        return None
+    try:
+        stop = int(optic.surfaces.stop_index)
+    except ValueError as exc:
+        _why("aim", str(exc))
+        return None
+    infinite = math.isinf(packer._f(optic.object_surface.geometry.cs.z))
+    first = 1 if infinite else 0
+    if table.reference_newton_surfaces(first, stop):
+        _why("aim", "reference-rule Newton surfaces")
+        return None
+    dev = eng.device
+    r_stop, jac, raygen, field_points = _aim_scalars(self, comp, table, w, stop, infinite)
+    kw = dict(first=first, stop=stop, stop_radius=r_stop, jacobian=jac, infinite=infinite,
+              tol=float(self.tol), max_iter=int(self.max_iter), check_status=False)
+    start = list(initial_guess) if initial_guess else None
+    if start is None and raygen and not any(f[2] or f[3] for f in field_points):
+        # iterative.py:90-104: the paraxial aimer's launch state, formed in the kernel by the
+        # generator the trace kernels use (an unvignetted optic: vx = vy = 1 whatever the field)
+        planes = _aim_planes(list(fields) + list(pupil_coords), dev)
+        if planes is None:
+            _why("aim", "inputs that are not arrays of one length on the device")
+            return None
+        kw.update(field=(planes[0], planes[1]), raygen=raygen)
+        px, py = planes[2], planes[3]
+    else:
+        if start is None:   # ... or by the reference's own code
+            Hx, Hy = (be.as_array_1d(v) for v in fields)
+            Px, Py = (be.as_array_1d(v) for v in pupil_coords)
+            start = list(self._paraxial_aimer.aim_rays((Hx, Hy), wavelengths, (Px, Py)))
+        if len(start) != 6:
+            _why("aim", "a start that is not six arrays")
+            return None
+        planes = _aim_planes(start + list(pupil_coords), dev)
+        if planes is None:
+            _why("aim", "inputs that are not arrays of one length on the device")
+            return None
+        kw.update(guess=planes[:6])
+        px, py = planes[6], planes[7]
+    out = eng.aim_rays(px, py, table.wavelength_index(w), **kw)
+    STATS["aim"] += 1
+    bits = int(eng._status.item())
+    eng.raise_for_status(bits)
+    eng.raise_for_aim_status(bits)
+    return tuple(out)
+
+
 # --------------------------------------------------------------------------- (de)activate
 # The seams replace PRIVATE methods of the reference.  Each entry: key in _ORIG -> (module,
 # class, method, the parameter names the replacement was written against, replacement).  A
@@ -1587,6 +1778,9 @@ _SEAMS = {
     "smtf": ("optiland.mtf.sampled", "SampledMTF", "calculate_mtf", ("self", "frequencies"),
              "_sampled_mtf_calculate"),
     "mmdft": ("optiland.psf.mmdft", "MMDFTPSF", "_compute_psf", ("self",), "_mmdft_compute_psf"),
+    "aim": ("optiland.rays.ray_aiming.iterative", "IterativeRayAimer", "aim_rays",
+            ("self", "fields", "wavelengths", "pupil_coords", "initial_guess"),
+            "_iterative_aim_rays"),
 }
 def _constructor_scope(key):
     """A constructor of the reference that only READS its optic -- `Wavefront.__init__`

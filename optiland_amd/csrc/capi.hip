@@ -20,6 +20,7 @@
 #include "../../include/optiland_hip.h"
 #include "device_table.h"
 #include "last_error.h"
+#include "system_view.h"
 #include "trace_launch.h"
 
 namespace {
@@ -741,6 +742,20 @@ int do_trace_opd(const ol_system* sys, const DeviceTable<T>& tab, int64_t n,
 }
 
 }  // namespace
+
+// system_view.h: the fp64 table and the validation facts of a system for the entry points that
+// live in translation units of their own (ray_aim.hip)
+namespace ol {
+SystemView system_view(const ol_system* sys) {
+  return SystemView{sys->n_surf,        sys->n_wl,      sys->device,
+                    sys->consistent,    sys->f64.surf,  sys->f64.cold,
+                    sys->f64.optics,    sys->f64.coeffs, sys->interaction.data(),
+                    sys->coating.data(), sys->ref_newton.data()};
+}
+int system_newton_family(const ol_system* sys, int32_t first, int32_t last) {
+  return newton_family(sys, first, last);
+}
+}  // namespace ol
 
 extern "C" {
 

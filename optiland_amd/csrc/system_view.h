@@ -1,0 +1,31 @@
+// system_view.h -- what a translation unit other than capi.hip may know of an `ol_system`: the
+// fp64 device table and the host-side facts the entry points validate against.  `ol_system`
+// itself stays private to capi.hip, which defines the two functions below; capi.hip references
+// no symbol of the units that use them (tests/hostmath links it alone).
+#pragma once
+#include <stdint.h>
+
+#include "../../include/optiland_hip.h"
+#include "device_table.h"
+
+namespace ol {
+
+struct SystemView {
+  int32_t n_surf, n_wl;
+  int device;
+  bool consistent;   // false after a failed ol_system_update: every entry point refuses it
+  const DevSurfHot<double>* surf;
+  const DevSurfCold<double>* cold;
+  const DevOptics<double>* optics;   // [n_surf][n_wl]
+  const double* coeffs;
+  const int32_t* interaction;        // host copies, [n_surf]
+  const int32_t* coating;
+  const uint8_t* ref_newton;         // OL_SURF_REFERENCE_NEWTON on a traced Newton surface
+};
+
+// `sys` must not be NULL
+SystemView system_view(const ol_system* sys);
+// the Newton kernel family of [first, last] (device_table.h kNr*), as ol_trace chooses it
+int system_newton_family(const ol_system* sys, int32_t first, int32_t last);
+
+}  // namespace ol

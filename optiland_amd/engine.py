@@ -1097,8 +1097,8 @@ class HipSystem:
             )
 
     # ------------------------------------------------------------- ray source
-    def _raygen_params(self):
-        rg = self.table.raygen
+    def _raygen_params(self, rg=None):
+        rg = self.table.raygen if rg is None else rg
         if not rg:
             raise ValueError("this SystemTable carries no ray-generation scalars")
         return _capi.RaygenParams(int(rg["object_infinite"]), int(rg.get("field_kind", 0)),
@@ -1574,6 +1574,70 @@ class HipSystem:
         self._check(rc, "ol_spot_max_r2")
         return out
 
+    # ------------------------------------------------------------- ray aiming
+    def can_aim_rays(self) -> bool:
+        return _capi.has_aim_rays(self.lib)
+
+    @staticmethod
+    def raise_for_aim_status(status: int) -> None:
+        """OL_AIM_* bits -> the two ValueErrors of rays/ray_aiming/iterative.py:141-145 and
+        :278-279, same texts, in the reference's order (the NaN check precedes the loop)."""
+        if status & _capi.AIM_NAN_GUESS:
+            raise ValueError(AIM_NAN_GUESS_TEXT)
+        if status & _capi.AIM_NOT_CONVERGED:
+            raise ValueError(AIM_NOT_CONVERGED_TEXT)
+
+    def aim_rays(self, px, py, wavelength_index: int = 0, *, first: int, stop: int,
+                 stop_radius: float, jacobian: float, infinite: bool, tol: float = 1e-6,
+                 max_iter: int = 10, guess=None, field=None, vig=(1.0, 1.0), flags: int = 0,
+                 raygen: dict | None = None, want_updates: bool = False,
+                 check_status: bool = True):
+        """`ol_aim_rays`: iterative ray aiming (rays/ray_aiming/iterative.py:60-281) in one launch,
+        fp64.  px, py: the pupil planes.  The start is either `guess` -- six planes x, y, z, L, M,
+        N, the reference's `initial_guess` -- or the paraxial launch state of `field` = (hx, hy)
+        (floats, or two planes) with `vig` = (1 - vx, 1 - vy), generated in the kernel from the
+        table's ray-generation scalars (or `raygen`, the same dictionary, for a table that was
+        packed without them).  Surfaces [first, stop] are traced; the target is
+        (px, py) * stop_radius in the stop surface's frame.  Returns the six solved planes, with
+        `want_updates` also the int32 plane of steps that moved each ray.  `check_status`: read
+        the status word back and raise what the reference raises (`raise_for_status`, then the
+        aimer's two ValueErrors); otherwise the bits stay in `self._status` for the caller."""
+        n = _aim_arguments(self.device, self.num_surfaces, px, py, guess, field, vig, first, stop,
+                           stop_radius, jacobian, tol, max_iter)
+        if not self.can_aim_rays():
+            raise _capi.HipExtensionError(
+                f"{_capi.library_path()} has no ol_aim_rays; rebuild the library "
+                "(`python -c 'import __graft_entry__ as g; g.build()'`)")
+        p = _capi.AimParams(float(stop_radius), float(jacobian), float(tol), int(max_iter),
+                            1 if infinite else 0,
+                            self._raygen_params(raygen) if guess is None
+                            else _capi.RaygenParams())
+        buf = torch.empty((6, max(n, 1)), dtype=torch.float64, device=self.device)
+        out = [buf[k, :n] for k in range(6)]
+        updates = torch.empty(n, dtype=torch.int32, device=self.device) if want_updates else None
+        self._status.zero_()
+        if n:
+            if guess is None:
+                hx, hy = field
+                inp, keep = self._raygen_inputs(hx, hy, px, py, vig[0], vig[1], flags)
+                gp = None
+            else:
+                inp, keep = self._raygen_inputs(None, None, px, py, None, None, 0)
+                keep += [g.contiguous() for g in guess]
+                gp = (C.c_void_p * 6)(*[g.data_ptr() for g in keep[-6:]])
+            op = (C.c_void_p * 6)(*[t.data_ptr() for t in out])
+            with self._device_ctx():
+                rc = self.lib.ol_aim_rays(self._handle, n, int(wavelength_index), int(first),
+                                          int(stop), C.byref(p), C.byref(inp), gp, op,
+                                          updates.data_ptr() if updates is not None else None,
+                                          self._status.data_ptr(), self._stream())
+            self._check(rc, "ol_aim_rays")
+            if check_status:
+                bits = int(self._status.item())
+                self.raise_for_status(bits)
+                self.raise_for_aim_status(bits)
+        return (out, updates) if want_updates else out
+
     def huygens_sum(self, *args, **kwargs):
         """`huygens_sum` (module level) on this system's device."""
         return huygens_sum(*args, device=self.device, **kwargs)
@@ -1581,6 +1645,58 @@ class HipSystem:
     def mmdft_psf(self, *args, **kwargs):
         """`mmdft_psf` (module level) on this system's device."""
         return mmdft_psf(*args, device=self.device, **kwargs)
+
+
+# rays/ray_aiming/iterative.py:141-145 and :278-279, verbatim
+AIM_NAN_GUESS_TEXT = ("Initial ray aiming guess produced NaNs. "
+                      "Consider using the 'robust' method instead.")
+AIM_NOT_CONVERGED_TEXT = "Iterative aimer failed to converge."
+
+
+def _aim_arguments(device, num_surfaces, px, py, guess, field, vig, first, stop, stop_radius,
+                   jacobian, tol, max_iter) -> int:
+    """The host-side checks of `HipSystem.aim_rays` (nothing here touches a device): the number
+    of rays."""
+    def plane(name, t, n=None):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 1:
+            raise ValueError(f"aim_rays: {name} must be a 1-D float64 tensor")
+        if n is not None and t.numel() != n:
+            raise ValueError(f"aim_rays: {name} has {t.numel()} elements, px has {n}")
+        if t.device != device:
+            raise ValueError(f"aim_rays: {name} lives on {t.device}, the system on {device}")
+        return int(t.numel())
+
+    n = plane("px", px)
+    plane("py", py, n)
+    if (guess is None) == (field is None):
+        raise ValueError("aim_rays: give either a guess (six planes) or a field (hx, hy)")
+    if guess is not None:
+        guess = list(guess)
+        if len(guess) != 6:
+            raise ValueError(f"aim_rays: a guess is six planes x, y, z, L, M, N, got {len(guess)}")
+        for name, g in zip(("x", "y", "z", "L", "M", "N"), guess):
+            plane(f"guess {name}", g, n)
+    else:
+        if len(field) != 2 or len(vig) != 2:
+            raise ValueError("aim_rays: field is (hx, hy) and vig is (1 - vx, 1 - vy)")
+        for pair, names in ((field, ("hx", "hy")), (vig, ("vx", "vy"))):
+            if isinstance(pair[0], torch.Tensor) != isinstance(pair[1], torch.Tensor):
+                raise ValueError(f"aim_rays: {names[0]} and {names[1]} must both be planes or "
+                                 "both scalars")
+            if isinstance(pair[0], torch.Tensor):
+                plane(names[0], pair[0], n)
+                plane(names[1], pair[1], n)
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter \
+            or not 0 <= int(max_iter) <= _capi.AIM_MAX_ITER:
+        raise ValueError(f"aim_rays: max_iter {max_iter!r} must be an integer in "
+                         f"[0, {_capi.AIM_MAX_ITER}]")
+    if not (np.isfinite(tol) and tol >= 0):
+        raise ValueError(f"aim_rays: tol {tol!r} must be finite and not negative")
+    if np.isnan(stop_radius) or np.isnan(jacobian):
+        raise ValueError(f"aim_rays: stop_radius {stop_radius!r} / jacobian {jacobian!r} is NaN")
+    if not 0 <= int(first) <= int(stop) < num_surfaces:
+        raise ValueError(f"aim_rays: surface range [{first}, {stop}] outside [0, {num_surfaces})")
+    return n
 
 
 def _analysis_library(has, symbols: str):

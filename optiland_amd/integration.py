@@ -507,6 +507,7 @@ _TRACER_VOLATILE = {
     "_hip_engines": collections.OrderedDict, "_hip_memo": collections.OrderedDict,
     "_hip_surface_cache": dict, "_hip_engine": lambda: None, "_hip_table": lambda: None,
     "_hip_trusted": lambda: None, "_hip_trust_depth": lambda: 0,
+    "_hip_aim_memo": dict,   # analysis_seams._aim_scalars: keyed by this process's tokens
 }
 
 

@@ -575,6 +575,8 @@ def _pack_optic(optic, wavelengths, name, tokens, cache, keep) -> SystemTable:
                           cache=cache, keep=keep)
     _pack_raygen(optic, table, tokens, cache)
     table.primary_wavelength = _f(optic.primary_wavelength)
+    table.stop_index = next((i for i, s in enumerate(optic.surfaces)
+                             if getattr(s, "is_stop", False)), None)
     pol = optic.polarization
     if pol != "ignore":
         st = optic.polarization_state
@@ -666,7 +668,7 @@ def _pack_apodization(ap):
 
 
 def _compute_raygen(optic, table: SystemTable, host_only: bool = False, tokens=None,
-                    cache=None) -> bool:
+                    cache=None, any_mode: bool = False) -> bool:
     """Scalars for on-device ray generation.  `host_only`: give up
     (return False, table untouched) as soon as the reference's paraxial tracer would have to
     be asked; otherwise True.
@@ -677,7 +679,9 @@ def _compute_raygen(optic, table: SystemTable, host_only: bool = False, tokens=N
     (paraxial_image_height.py:19-60), incl. the object-space-telecentric branch of the
     aimer (rays/ray_aiming/paraxial.py:33-106).  Otherwise (iterative / robust aiming,
     real image height fields) `table.raygen` stays empty and callers generate rays with
-    the reference's own RayGenerator.
+    the reference's own RayGenerator.  `any_mode`: pack the PARAXIAL aimer's scalars whatever
+    the optic's aiming mode is -- the iterative solve starts from that aimer's launch state
+    (`paraxial_start_scalars`).
     """
     fd = optic.fields.field_definition
     kind = {"AngleField": S.FIELD_ANGLE, "ObjectHeightField": S.FIELD_OBJECT_HEIGHT,
@@ -688,7 +692,7 @@ def _compute_raygen(optic, table: SystemTable, host_only: bool = False, tokens=N
     if apod is None:
         return True
     mode = getattr(optic.ray_tracer, "ray_aiming_config", {}).get("mode", "paraxial")
-    if mode != "paraxial":
+    if mode != "paraxial" and not any_mode:
         return True
     obj = optic.object_surface
     # surfaces/object_surface.py:48-50 `is_infinite` = isinf(cs.z), read through the packer's
@@ -771,6 +775,19 @@ def _compute_raygen(optic, table: SystemTable, host_only: bool = False, tokens=N
     except Exception:  # systems without a well-defined exit pupil: no wavefront data
         pass
     return True
+
+
+def paraxial_start_scalars(optic, table: SystemTable):
+    """(raygen, fields) as `pack_optic` would leave them on `table` under PARAXIAL aiming -- for
+    an optic in any aiming mode, `table` itself untouched.  The start of the iterative solve
+    (rays/ray_aiming/iterative.py:90-104) is the paraxial aimer's launch state, which the device
+    generator forms from these scalars.  ({}, []) where it does not cover the optic."""
+    import copy
+
+    scratch = copy.copy(table)
+    scratch.raygen, scratch.fields = {}, []
+    _compute_raygen(optic, scratch, any_mode=True)
+    return scratch.raygen, scratch.fields
 
 
 _HOST_PARAXIAL_GEOMS = frozenset((S.GEOM_PLANE, S.GEOM_STANDARD, S.GEOM_EVEN_ASPHERE,

@@ -144,6 +144,7 @@ class SystemTable:
     name: str = ""
     last_thickness: float = 0.0  # optic.surfaces[-1].thickness
     primary_wavelength: float | None = None  # optic.primary_wavelength (microns), if known
+    stop_index: int | None = None  # optic.surfaces.stop_index (ray aiming), if known
 
     # ------------------------------------------------------------------ info
     def reference_wavelength_index(self, wavelengths=None) -> int:
@@ -243,6 +244,8 @@ class SystemTable:
         }
         if self.primary_wavelength is not None:
             doc["primary_wavelength"] = float(self.primary_wavelength)
+        if self.stop_index is not None:
+            doc["stop_index"] = int(self.stop_index)
         return json.dumps(doc, indent=1)
 
     @classmethod
@@ -274,6 +277,7 @@ class SystemTable:
             name=doc.get("name", ""),
             last_thickness=_dec(doc.get("last_thickness", 0.0)),
             primary_wavelength=doc.get("primary_wavelength"),
+            stop_index=doc.get("stop_index"),
         )
 
     def save(self, path) -> None:

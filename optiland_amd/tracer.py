@@ -215,12 +215,59 @@ class HipRayTracer:
 
     # ------------------------------------------------------------ configuration
     def set_aiming(self, mode: str, max_iter: int = 10, tol: float = 1e-6, **kwargs):
-        """real_ray_tracer.py:42-56.  Only paraxial aiming runs on device."""
+        """real_ray_tracer.py:42-56.  Only paraxial aiming is a MODE of this tracer: the
+        iterative solve needs a stop radius and a paraxial Jacobian, which the reference takes
+        from the optic and a packed table does not carry -- `aim_rays` runs it with both given."""
         if mode != "paraxial":
             raise NotImplementedError(
-                f"ray aiming mode {mode!r} is a host-side Newton loop in the reference "
-                "(rays/ray_aiming/iterative.py) and is outside the fused path")
+                f"ray aiming mode {mode!r} is outside the fused path: a packed table has no "
+                "optic to take the stop radius from (solve with `aim_rays`, trace the result "
+                "with `trace_rays`)")
         self.ray_aiming_config = {"mode": mode, "max_iter": max_iter, "tol": tol, **kwargs}
+
+    def aim_rays(self, hx, hy, px, py, wavelength, *, stop_radius: float, jacobian: float,
+                 tol: float = 1e-6, max_iter: int = 10, guess=None, stop_index: int | None = None,
+                 want_updates: bool = False):
+        """Iterative ray aiming (rays/ray_aiming/iterative.py:60-281) in one launch
+        (`ol_aim_rays`, fp64): the launch state (x, y, z, L, M, N) of every ray such that it
+        crosses the stop surface at (px, py) * stop_radius.  hx, hy: the field point (floats) or
+        per-ray planes; px, py: the pupil planes.  `stop_radius` and `jacobian` are the
+        reference's `get_stop_radius_strategy(optic, "iterative").calculate_stop_radius()` and
+        `IterativeRayAimer._get_paraxial_jacobian(...)`.  `guess`: six planes to start from
+        (the reference's `initial_guess`) instead of the paraxial launch state.  Raises the
+        reference's two ValueErrors.  The result feeds `trace_rays`; its direction cosines are
+        not renormalised, as in the reference."""
+        eng = self.engine
+        if not hasattr(eng, "aim_rays"):
+            raise NotImplementedError("this engine has no ray aiming (ol_aim_rays)")
+        stop = self.table.stop_index if stop_index is None else stop_index
+        if stop is None:
+            raise ValueError("aim_rays: this SystemTable does not say which surface is the stop "
+                             "(pack it again with pack_optic, or pass stop_index)")
+        wl, _w = self._wavelength_index(wavelength)
+        infinite = bool(np.isinf(self.table.surfaces["origin"][0][2])) if not self.table.raygen \
+            else bool(self.table.raygen["object_infinite"])
+
+        def plane(v):
+            return v.to(device=self.device, dtype=torch.float64).reshape(-1).contiguous() \
+                if isinstance(v, torch.Tensor) else \
+                torch.as_tensor(np.atleast_1d(np.asarray(v, dtype=np.float64)),
+                                device=self.device).reshape(-1)
+
+        px, py = plane(px), plane(py)
+        kw = dict(first=1 if infinite else 0, stop=int(stop), stop_radius=stop_radius,
+                  jacobian=jacobian, infinite=infinite, tol=tol, max_iter=max_iter,
+                  want_updates=want_updates)
+        if guess is not None:
+            return eng.aim_rays(px, py, wl, guess=[plane(g) for g in guess], **kw)
+        shx, shy = self._as_scalar(hx), self._as_scalar(hy)
+        if shx is not None and shy is not None:
+            return eng.aim_rays(px, py, wl, field=(shx, shy), vig=self._vig_scalar(shx, shy), **kw)
+        n = int(px.numel())
+        hxp, hyp = (plane(v).expand(n).contiguous() for v in (hx, hy))
+        vx, vy = self._vig_factor(hxp.to(self.dtype), hyp.to(self.dtype))
+        vig = (1.0, 1.0) if vx is None else (plane(1.0 - vx), plane(1.0 - vy))
+        return eng.aim_rays(px, py, wl, field=(hxp, hyp), vig=vig, **kw)
 
     # ------------------------------------------------------------------ helpers
     def _dev(self, v):
