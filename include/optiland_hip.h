@@ -60,6 +60,29 @@ enum { OL_F32 = 0, OL_F64 = 1 };
  * TOROIDAL      optiland/geometries/toroidal.py:86-242; radius = YZ radius (base
  *               conic of the Newton start, conic = 0), coefficient block =
  *               {R_rot, k_yz, a_1, a_2, ...} (n_coeff = 2 + number of y^2i terms)
+ * FORBES_Q      optiland/geometries/forbes/geometry.py:184-443 (ForbesQNormalSlopeGeometry /
+ *               ForbesQbfsGeometry, surface type "forbes_qbfs") on the base conic radius / conic,
+ *               norm_radius = the normalisation radius (finite, > 0).  Coefficient block =
+ *               {b_0 .. b_{n_coeff-1}}: the radial terms AFTER the change of basis to the
+ *               orthonormal P_n (qpoly.py:87-115), done by the caller in double
+ * FORBES_Q2D    geometry.py:445-731 (ForbesQ2dGeometry, "forbes_q2d").  n_coeff = the LENGTH of
+ *               the block, which describes itself:
+ *                 n0, M, b_0 .. b_{n0-1},                       the m = 0 list as for FORBES_Q
+ *                 then for m = 1 .. M:  na, nb, na quads (the cosine list a^m), nb quads (the
+ *                 sine list b^m); quad n of a list = {d_n, A_n, B_n, C_{n+1}}: the coefficient
+ *                 in the P_n^m basis (qpoly.py:355-370) and the constants of the Clenshaw step
+ *                 alpha_n = d_n + (A_n + B_n u^2) alpha_{n+1} - C_{n+1} alpha_{n+2}
+ *                 (abc_q2d_clenshaw, qpoly.py:373-400: its special cases and its d == 0 ->
+ *                 1e-99 included); C = 0 in the last two quads of a list.
+ *               Counts are whole numbers stored as doubles; every count is >= 0 and the counts
+ *               must add up to n_coeff exactly.  There is no cap on the number of terms: the
+ *               kernel sweeps the lists in running registers.
+ *               Forbes rows are traced by ol_trace_forbes ONLY, one surface per launch: every
+ *               entry point that walks a surface range (ol_trace, ol_trace_ex, ol_newton_count,
+ *               ol_trace_generate, ol_trace_spot, ol_trace_spot_batch, ol_trace_opd,
+ *               ol_trace_opd_dev, ol_wavefront_reference, ol_aim_rays) returns OL_EUNSUPPORTED,
+ *               naming the surface, when its range holds one -- a caller cuts the range there.
+ *               (Additive: OL_ABI_VERSION is unchanged; look the entry up by name.)
  */
 typedef enum ol_geom_kind {
   OL_GEOM_PLANE = 0,
@@ -70,7 +93,9 @@ typedef enum ol_geom_kind {
   OL_GEOM_POLYNOMIAL = 5,
   OL_GEOM_CHEBYSHEV = 6,
   OL_GEOM_BICONIC = 7,
-  OL_GEOM_TOROIDAL = 8
+  OL_GEOM_TOROIDAL = 8,
+  OL_GEOM_FORBES_Q = 9,
+  OL_GEOM_FORBES_Q2D = 10
 } ol_geom_kind;
 
 /* ---- what happens at the surface ----------------------------------------
@@ -180,7 +205,7 @@ typedef struct ol_surface_desc {
   double radius;         /* radius of curvature (may be +-inf)                */
   double conic;          /* conic constant k                                  */
   double tol;            /* Newton-Raphson tolerance (geometry.tol)           */
-  double norm_radius;    /* ZERNIKE normalisation radius                      */
+  double norm_radius;    /* ZERNIKE / FORBES_Q / FORBES_Q2D normalisation radius */
   double origin[3];      /* global position of the local origin               */
   double rot[9];         /* row-major R: local = R * (global - origin)
                             (= Rx(-rx) Ry(-ry) Rz(-rz), with parent frames
@@ -361,6 +386,24 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays,
                 void* record, int64_t record_stride, void* prt,
                 int32_t first_surface, int32_t last_surface, uint32_t flags,
                 uint32_t* status, const ol_trace_extras* extras, void* stream);
+
+/* ONE Forbes surface (OL_GEOM_FORBES_Q / OL_GEOM_FORBES_Q2D) in one launch: what Surface.trace
+ * does there (surfaces/standard_surface.py:232-274 on geometries/forbes/geometry.py) -- into the
+ * surface's frame, the Newton-Raphson solve from the base conic's hit (newton_raphson.py:119-168,
+ * stopped PER RAY like every Newton geometry of ol_trace), propagation, absorption, OPD, aperture
+ * clip, refraction / reflection, SimpleCoating, back to the global frame.  Unpolarised only.
+ *   rays[8]     as for ol_trace: the state in the GLOBAL frame (what ol_trace writes back with
+ *               OL_TRACE_WRITE_RAYS); rewritten iff OL_TRACE_WRITE_RAYS
+ *   record_row  nullable; ONE row of a record block: plane k at record_row + k * record_stride
+ *   surface     index of the Forbes row (OL_EINVAL for any other geometry kind)
+ *   flags       OL_TRACE_WRITE_RAYS, OL_TRACE_MIDRANGE
+ *   status      nullable; OL_STATUS_NAN_DIRECTION as for the last surface of ol_trace, unless
+ *               OL_TRACE_MIDRANGE says that the caller goes on tracing behind this surface
+ * A surface with a Fresnel / polarizer / retarder coating is refused (OL_EUNSUPPORTED).       */
+#define OL_TRACE_MIDRANGE 0x40u
+int ol_trace_forbes(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const rays[8],
+                    int32_t wavelength_index, void* record_row, int64_t record_stride,
+                    int32_t surface, uint32_t flags, uint32_t* status, void* stream);
 
 /* ABI 11.  The iteration count of ONE reference-rule Newton surface for this batch of rays
  * (see OL_SURF_REFERENCE_NEWTON): the rays are traced from `first_surface` up to `surface` --

@@ -151,6 +151,7 @@ EXPORTS = (
     "ol_sampled_mtf",
     "ol_mmdft_psf",
     "ol_aim_rays",
+    "ol_trace_forbes",
 )
 
 F32, F64 = 0, 1
@@ -305,6 +306,10 @@ def bind(lib, path: str = "?"):
         lib.ol_aim_rays.restype = C.c_int
         lib.ol_aim_rays.argtypes = [vp, i64, i32, i32, i32, vp, vp, C.POINTER(vp), C.POINTER(vp),
                                     vp, vp, vp]
+    if has_trace_forbes(lib):   # (additive within ABI 11, like ol_huygens_psf)
+        lib.ol_trace_forbes.restype = C.c_int
+        lib.ol_trace_forbes.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, vp, i64, i32, u32,
+                                        vp, vp]
     return lib
 
 
@@ -346,6 +351,15 @@ class AimParams(C.Structure):
 def has_aim_rays(lib) -> bool:
     """True when the loaded library exports ol_aim_rays."""
     return hasattr(lib, "ol_aim_rays")
+
+
+GEOM_FORBES_Q, GEOM_FORBES_Q2D = 9, 10   # OL_GEOM_FORBES_* (optiland_hip.h)
+TRACE_MIDRANGE = 0x40                     # OL_TRACE_MIDRANGE
+
+
+def has_trace_forbes(lib) -> bool:
+    """True when the loaded library exports ol_trace_forbes."""
+    return hasattr(lib, "ol_trace_forbes")
 
 
 def has_huygens(lib) -> bool:

@@ -392,6 +392,17 @@ int newton_family(const ol_system* sys, int32_t first, int32_t last) {
   return 1;
 }
 
+// Forbes rows (OL_GEOM_FORBES_Q / _Q2D) are traced by ol_trace_forbes alone (forbes.hip): the
+// fused kernels carry no functor for them, so every entry point that walks a surface range
+// answers a range that holds one here, before any launch
+int refuse_forbes(const char* who, const ol_system* sys, int32_t first, int32_t last) {
+  for (int32_t s = first; s <= last; ++s)
+    if (ol::is_forbes_kind(sys->geom[s]))
+      return failf(OL_EUNSUPPORTED, "%s: surface %d is a Forbes surface: trace it with "
+                                    "ol_trace_forbes and cut the range there", who, s);
+  return OL_OK;
+}
+
 template <typename T>
 int do_trace(const ol_system* sys, const DeviceTable<T>& tab, int64_t n, void* const rays[8],
              int32_t wl, void* record, int64_t record_stride, void* prt, int32_t first,
@@ -455,6 +466,7 @@ int do_trace(const ol_system* sys, const DeviceTable<T>& tab, int64_t n, void* c
 // the fused entry points (one launch: generate -> trace [-> reduce]) do not serve ranges whose
 // Newton iteration count is a property of the batch
 int refuse_reference_newton(const char* who, const ol_system* sys) {
+  if (int rc = refuse_forbes(who, sys, 0, sys->n_surf - 1)) return rc;
   if (newton_family(sys, 0, sys->n_surf - 1) != ol::kNrReference) return OL_OK;
   return failf(OL_EUNSUPPORTED, "%s: the system carries OL_SURF_REFERENCE_NEWTON surfaces "
                                 "(reference stop rule): generate with ol_generate_rays, count "
@@ -750,7 +762,9 @@ SystemView system_view(const ol_system* sys) {
   return SystemView{sys->n_surf,        sys->n_wl,      sys->device,
                     sys->consistent,    sys->f64.surf,  sys->f64.cold,
                     sys->f64.optics,    sys->f64.coeffs, sys->interaction.data(),
-                    sys->coating.data(), sys->ref_newton.data()};
+                    sys->coating.data(), sys->ref_newton.data(), sys->geom.data(),
+                    sys->f32.surf,      sys->f32.cold,  sys->f32.optics,
+                    sys->f32.coeffs};
 }
 int system_newton_family(const ol_system* sys, int32_t first, int32_t last) {
   return newton_family(sys, first, last);
@@ -808,7 +822,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     const ol_surface_desc& s = surf[i];
     HostSurf& d = dev[i];
     std::memset(&d, 0, sizeof(d));
-    if (s.geom_kind < OL_GEOM_PLANE || s.geom_kind > OL_GEOM_TOROIDAL)
+    if (s.geom_kind < OL_GEOM_PLANE || s.geom_kind > OL_GEOM_FORBES_Q2D)
       return failf(OL_EUNSUPPORTED, "surface %d: geometry kind %d", i, s.geom_kind);
     if (s.interaction < OL_INTERACT_RECORD_ONLY || s.interaction > OL_INTERACT_REFLECT)
       return failf(OL_EUNSUPPORTED, "surface %d: interaction %d", i, s.interaction);
@@ -824,6 +838,8 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
       return failf(OL_EINVAL, "surface %d: coefficient block exceeds the buffer", i);
 
     d.geom = s.geom_kind;
+    if (s.geom_kind == OL_GEOM_FORBES_Q) d.geom = ol::kGeomForbesQ;   // (9 is kGeomZernikeMono)
+    if (s.geom_kind == OL_GEOM_FORBES_Q2D) d.geom = ol::kGeomForbesQ2d;
     d.interaction = s.interaction;
     d.aperture_kind = s.aperture_kind;
     d.coating_kind = s.coating_kind;
@@ -972,6 +988,57 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
       dcoef.push_back(1.0 + src[1]);
       dcoef.push_back((std::isfinite(Ryz) && Ryz != 0.0) ? 1.0 / Ryz : 0.0);
       dcoef.insert(dcoef.end(), src + 2, src + s.n_coeff);
+    } else if (ol::is_forbes_kind(s.geom_kind)) {
+      // device block: n0, norm_radius, then the rest of the public block (forbes_device.h)
+      if (!(s.norm_radius > 0.0) || !std::isfinite(s.norm_radius))
+        return failf(OL_EINVAL, "surface %d: Forbes norm_radius %g must be finite and positive", i,
+                     s.norm_radius);
+      if (s.interaction == OL_INTERACT_RECORD_ONLY)
+        return failf(OL_EUNSUPPORTED, "surface %d: a Forbes surface that only records", i);
+      for (int k = 0; k < s.n_coeff; ++k)
+        if (!std::isfinite(src[k]))
+          return failf(OL_EINVAL, "surface %d: Forbes coefficient block entry %d is not finite", i, k);
+      d.n_coeff = s.n_coeff;
+      if (s.geom_kind == OL_GEOM_FORBES_Q) {
+        int_slots.push_back(dcoef.size());
+        dcoef.push_back((double)s.n_coeff);
+        dcoef.push_back(s.norm_radius);
+        dcoef.insert(dcoef.end(), src, src + s.n_coeff);
+      } else {
+        // the block describes itself: walk it once, every count against what is left
+        auto count_at = [&](int64_t at, int64_t& v) {
+          if (at >= s.n_coeff) return false;
+          const double c = src[at];
+          if (!(c >= 0.0) || c > (double)s.n_coeff || c != std::floor(c)) return false;
+          v = (int64_t)c;
+          return true;
+        };
+        const size_t base = dcoef.size();
+        std::vector<size_t> ints;
+        int64_t n0 = 0, M = 0, at = 2;
+        bool ok = count_at(0, n0) && count_at(1, M) && at + n0 <= s.n_coeff;
+        if (ok) {
+          ints.push_back(0);           // n0        (device offsets: + 1 behind norm_radius)
+          ints.push_back(2);           // M
+          at += n0;
+          for (int64_t mm = 0; ok && mm < M; ++mm) {
+            int64_t na = 0, nb = 0;
+            ok = count_at(at, na) && count_at(at + 1, nb) && at + 2 + 4 * (na + nb) <= s.n_coeff;
+            if (ok) {
+              ints.push_back((size_t)at + 1);
+              ints.push_back((size_t)at + 2);
+              at += 2 + 4 * (na + nb);
+            }
+          }
+        }
+        if (!ok || at != s.n_coeff)
+          return failf(OL_EINVAL, "surface %d: Forbes Q2D block of %d values does not match the "
+                                  "counts it declares", i, s.n_coeff);
+        dcoef.push_back(src[0]);
+        dcoef.push_back(s.norm_radius);
+        dcoef.insert(dcoef.end(), src + 1, src + s.n_coeff);
+        for (size_t k : ints) int_slots.push_back(base + k);
+      }
     } else {
       d.n_coeff = 0;
     }
@@ -1123,6 +1190,7 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const r
   if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
     return failf(OL_EINVAL, "ol_trace: wavelength index %d outside [0, %d)", wavelength_index,
                  sys->n_wl);
+  if (int rc = refuse_forbes("ol_trace", sys, first_surface, last_surface)) return rc;
   if (n_rays == 0) return OL_OK;
   {
     int cur = -1;
@@ -1181,6 +1249,7 @@ int ol_newton_count(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* con
     return failf(OL_EINVAL, "ol_newton_count: wavelength index %d outside [0, %d)",
                  wavelength_index, sys->n_wl);
   if (!iterations) return failf(OL_EINVAL, "ol_newton_count: iterations is NULL");
+  if (int rc = refuse_forbes("ol_newton_count", sys, first_surface, surface)) return rc;
   if (!sys->ref_newton[surface])
     return failf(OL_EINVAL, "ol_newton_count: surface %d is not a traced Newton-Raphson surface "
                             "with OL_SURF_REFERENCE_NEWTON", surface);

@@ -91,7 +91,11 @@ enum : int {
   kGeomToroidal = 8,   // block: {R_rot (or inf), 1/R_rot, 1 + k_yz, c_yz, a_1, a_2, ...}
   // internal (never in ol_surface_desc): a Zernike surface of low order re-expressed by
   // ol_system_create as one bivariate polynomial of degree n_coeff in (x, y) / norm_radius
-  kGeomZernikeMono = 9
+  kGeomZernikeMono = 9,
+  // OL_GEOM_FORBES_Q (9) / OL_GEOM_FORBES_Q2D (10) of ol_surface_desc, renumbered: such rows are
+  // traced by forbes.hip alone and never reach the fused kernels' dispatch (forbes_device.h)
+  kGeomForbesQ = 16,
+  kGeomForbesQ2d = 17
 };
 enum : int { kRecordOnly = 0, kRefract = 1, kReflect = 2 };
 enum : int {

@@ -49,6 +49,10 @@ inline int aim_check(const ol_system* sys, int64_t n_rays, int32_t wavelength_in
   if (std::isnan(p->stop_radius) || std::isnan(p->jacobian))
     return failf(OL_EINVAL, "ol_aim_rays: stop_radius %g / jacobian %g is NaN", p->stop_radius,
                  p->jacobian);
+  for (int32_t s = first_surface; s <= stop_surface; ++s)
+    if (is_forbes_kind(v.geom[s]))
+      return failf(OL_EUNSUPPORTED, "ol_aim_rays: surface %d is a Forbes surface (traced by "
+                                    "ol_trace_forbes only)", s);
   // a batch-global stop rule has no per-ray form
   for (int32_t s = first_surface; s <= stop_surface; ++s)
     if (v.ref_newton[s])

@@ -21,7 +21,14 @@ struct SystemView {
   const int32_t* interaction;        // host copies, [n_surf]
   const int32_t* coating;
   const uint8_t* ref_newton;         // OL_SURF_REFERENCE_NEWTON on a traced Newton surface
+  const int32_t* geom;               // ol_geom_kind as given, [n_surf]
+  const DevSurfHot<float>* surf32;   // the fp32 table (forbes.hip)
+  const DevSurfCold<float>* cold32;
+  const DevOptics<float>* optics32;
+  const float* coeffs32;
 };
+
+inline bool is_forbes_kind(int32_t g) { return g == OL_GEOM_FORBES_Q || g == OL_GEOM_FORBES_Q2D; }
 
 // `sys` must not be NULL
 SystemView system_view(const ol_system* sys);

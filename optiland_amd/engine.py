@@ -452,6 +452,34 @@ def _start_sweeper() -> None:
     t.start()
 
 
+def split_trace(forbes, first: int, last: int, rec, rec_first: int, fused, one) -> None:
+    """Walk surfaces [first, last] as fused runs and single Forbes launches, in order.
+
+    forbes: the table's Forbes rows (`SystemTable.forbes`).  rec: the caller's record block or
+    None; its row 0 holds surface `rec_first`.  `fused(a, b, rec_view, rec_from, midrange)` traces
+    the run [a, b] -- `rec_view` is the part of the block whose row 0 is surface `rec_from`, or
+    None when the run lies in front of the first recorded surface; `one(s, row, midrange)` traces
+    the Forbes surface s (`row`: its (8, stride) row of the block, or None).  Both carry the ray
+    state in the SAME eight planes (written back after every launch); `midrange`: the trace goes
+    on behind this launch.  One splitter for stand-alone callers and for the drop-in's bridge."""
+    cut = set(forbes)
+    s = first
+    while s <= last:
+        if s in cut:
+            one(s, rec[s - rec_first] if rec is not None and s >= rec_first else None, s < last)
+            s += 1
+            continue
+        e = s
+        while e + 1 <= last and (e + 1) not in cut:
+            e += 1
+        if rec is not None and e >= rec_first:
+            r0 = max(s, rec_first)
+            fused(s, e, rec[r0 - rec_first:], r0, e < last)
+        else:
+            fused(s, e, None, None, e < last)
+        s = e + 1
+
+
 class HipSystem:
     """A surface table resident on one GPU (wraps `ol_system`)."""
 
@@ -778,8 +806,10 @@ class HipSystem:
               check_status: bool = True, prt_identity: bool = False,
               defer_status: bool = False, zero_status: bool = True,
               spot=None, record_first: int | None = None,
-              nonunit_directions: bool = False) -> TraceResult:
-        """Launch the fused trace.
+              nonunit_directions: bool = False, _status_to=None) -> TraceResult:
+        """Launch the fused trace.  A range that holds Forbes rows (`table.forbes`) is split into
+        fused runs and one `trace_forbes` launch per such row, all writing into the same record
+        block and status word (unpolarised, no spot epilogue).
 
         rays: sequence of 8 contiguous 1-D device tensors (x,y,z,L,M,N,i,opd) of one
         dtype -- the initial state.  record: True (allocate), False/None, or a
@@ -824,6 +854,13 @@ class HipSystem:
                 raise ValueError("record must be a contiguous (rows, 8, stride>=n) tensor")
         if write_rays is None:
             write_rays = rec is None
+        if self.table.forbes and any(first <= f <= last for f in self.table.forbes):
+            if prt is not None or spot is not None:
+                raise ValueError("a range with Forbes surfaces is traced unpolarised and without "
+                                 "the spot epilogue (cut it at those surfaces)")
+            return self._trace_split(rays, int(wavelength_index), rec, rec_first, int(first),
+                                     int(last), write_rays, check_status, defer_status,
+                                     zero_status)
         flags = (S.TRACE_WRITE_RAYS if write_rays else 0) | S.TRACE_COMPACT \
             | _few_waves_flag(rec) | _hot_loop_flag(rec)
         if prt is not None:
@@ -862,8 +899,9 @@ class HipSystem:
             ex.newton_iterations = iters.data_ptr()
         if ex is not None:
             extras = C.byref(ex)
+        status_word = self._status if _status_to is None else _status_to
         if check_status and zero_status:  # zero_status=False: keep bits set by ray generation
-            self._status.zero_()
+            status_word.zero_()
         with self._device_ctx():
             rc = self.lib.ol_trace_ex(
                 self._handle, _DT[dtype], n, ptrs, int(wavelength_index),
@@ -871,14 +909,102 @@ class HipSystem:
                 int(rec.shape[2]) if rec is not None else 0,
                 prt.data_ptr() if prt is not None else None,
                 int(first), int(last), flags,
-                self._status.data_ptr() if check_status else None,
+                status_word.data_ptr() if check_status else None,
                 extras, self._stream())
         self._check(rc, "ol_trace")
         # defer_status: the kernel still ORs its bits into self._status, but the caller
         # reads them back later (together with other device-side checks)
-        status = int(self._status.item()) if (check_status and not defer_status) else 0
+        status = int(status_word.item()) if (check_status and not defer_status) else 0
         self.raise_for_status(status)
         return TraceResult(n, rays, rec, prt, status, rec_first if rec is not None else first,
+                           last)
+
+    # ---- Forbes surfaces (ol_trace_forbes: one surface, one launch) --------------------------
+    def can_trace_forbes(self) -> bool:
+        return _capi.has_trace_forbes(self.lib)
+
+    def trace_forbes(self, rays, surface: int, wavelength_index: int = 0, record_row=None,
+                     write_rays: bool | None = None, midrange: bool = False,
+                     check_status: bool = True, defer_status: bool = False,
+                     zero_status: bool = True) -> int:
+        """Trace the eight planes `rays` (global frame, as `trace` takes and leaves them) through
+        the ONE Forbes surface `surface` of the table (`ol_trace_forbes`): frame change, Newton
+        solve, interaction, back to the global frame.  record_row: an (8, stride >= n) tensor --
+        one row of a record block -- or None; write_rays (default: only when nothing is
+        recorded): the state is written back into `rays`.  midrange: the caller traces on behind
+        this surface (the informational STATUS_NAN_DIRECTION is then not raised here).  Returns
+        the status word (0 when deferred or unchecked).  A missing kernel is an error."""
+        if not self.can_trace_forbes():
+            raise _capi.HipExtensionError("the loaded library has no ol_trace_forbes: rebuild it")
+        rays = list(rays)
+        if len(rays) != 8:
+            raise ValueError("rays must be 8 planes: x,y,z,L,M,N,i,opd")
+        n = int(rays[0].numel())
+        dtype = rays[0].dtype
+        if dtype not in _DT:
+            raise TypeError(f"unsupported ray dtype {dtype}")
+        for t in rays:
+            if t.device != self.device or t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+                raise ValueError("ray planes must be contiguous, same dtype/size, on the system's device")
+        if int(surface) not in self.table.forbes:
+            raise ValueError(f"surface {surface} is not a Forbes row of this table")
+        row = record_row
+        if row is not None:
+            if row.dtype != dtype or row.dim() != 2 or row.shape[0] != 8 or row.shape[1] < n \
+                    or row.device != self.device or not row.is_contiguous():
+                raise ValueError("record_row must be a contiguous (8, stride>=n) tensor")
+        if write_rays is None:
+            write_rays = row is None
+        if row is None and not write_rays:
+            raise ValueError("nothing to write: no record_row and write_rays=False")
+        flags = (S.TRACE_WRITE_RAYS if write_rays else 0) | (S.TRACE_MIDRANGE if midrange else 0)
+        ptrs = (C.c_void_p * 8)(*[t.data_ptr() for t in rays])
+        if check_status and zero_status:
+            self._status.zero_()
+        with self._device_ctx():
+            rc = self.lib.ol_trace_forbes(
+                self._handle, _DT[dtype], n, ptrs, int(wavelength_index),
+                row.data_ptr() if row is not None else None,
+                int(row.shape[1]) if row is not None else 0, int(surface), flags,
+                self._status.data_ptr() if check_status else None, self._stream())
+        self._check(rc, "ol_trace_forbes")
+        status = int(self._status.item()) if (check_status and not defer_status) else 0
+        self.raise_for_status(status)
+        return status
+
+    def _trace_split(self, rays, wl, rec, rec_first, first, last, write_rays, check_status,
+                     defer_status, zero_status) -> TraceResult:
+        """`trace` over a range with Forbes rows (`split_trace`).  The state travels in `rays`
+        themselves (write_rays) or in a private copy of them; every launch ORs into the one
+        status word, except that what a fused run in FRONT of a later launch reports about its
+        own last surface (STATUS_NAN_DIRECTION) is dropped: it is not the end of this trace."""
+        n = int(rays[0].numel())
+        work = rays if write_rays else [t.clone() for t in rays]
+        if check_status and zero_status:
+            self._status.zero_()
+        mid = []
+
+        def fused(a, b, view, r0, midrange):
+            word = None
+            if check_status and midrange:
+                if not mid:
+                    mid.append(torch.zeros_like(self._status))
+                word = mid[0]
+            self.trace(work, wl, record=view if view is not None else False, first=a, last=b,
+                       write_rays=True, check_status=check_status, defer_status=True,
+                       zero_status=False, record_first=r0 if (r0 is not None and r0 != a) else None,
+                       _status_to=word)
+
+        def one(s, row, midrange):
+            self.trace_forbes(work, s, wl, record_row=row, write_rays=True, midrange=midrange,
+                              check_status=check_status, defer_status=True, zero_status=False)
+
+        split_trace(self.table.forbes, first, last, rec, rec_first, fused, one)
+        if mid:
+            self._status.bitwise_or_(mid[0].bitwise_and_(~S.STATUS_NAN_DIRECTION))
+        status = int(self._status.item()) if (check_status and not defer_status) else 0
+        self.raise_for_status(status)
+        return TraceResult(n, rays, rec, None, status, rec_first if rec is not None else first,
                            last)
 
     # ---- reference-rule Newton surfaces (ABI 11; newton_raphson.py:137-166) -----------------

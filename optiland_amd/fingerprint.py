@@ -25,7 +25,10 @@ exactly those objects and collects, without touching the device:
                                            polygon aperture is seen
   * lists / tuples                      -> element tokens
   * other objects                       -> (class name, id)  [identity]
-  * dicts                               -> ignored (the reference keeps caches in them)
+  * dicts                               -> ignored (the reference keeps caches in them) --
+                                           except the TERM dictionaries of a Forbes geometry
+                                           (`radial_terms`, `freeform_coeffs`), whose items are
+                                           part of the surface token: they ARE the prescription
 
 Tokens are compared with `==`; the objects whose ids appear in a token are kept alive
 next to it (`keep`) so that an id cannot be recycled while the token is cached.  What this
@@ -211,9 +214,33 @@ def _material(m, keep, memo):
     return (_obj(m, keep, memo), type(getattr(m, "propagation_model", None)).__name__)
 
 
+_FORBES_TERMS = ("radial_terms", "freeform_coeffs")
+
+
+def _forbes_terms(geom, keep):
+    """The term dictionaries of a Forbes geometry (geometries/forbes/geometry.py: `radial_terms`
+    of the Q surface, `freeform_coeffs` of the Q2D one) item by item, None for every other
+    geometry.  The one-level walk of `geom.__dict__` skips dicts, and the optimiser's variables
+    (optimization/variable/forbes_coeff.py) write exactly there; everything else the packer reads
+    of these classes -- norm_radius (the automatic `update_normalization` included), tol,
+    max_iter, the prepared cm0 / ams / bms lists -- is a scalar, an array or a list of the
+    geometry's own `__dict__` and is seen by that walk."""
+    d = getattr(geom, "__dict__", None)
+    if d is None:
+        return None
+    out = None
+    for name in _FORBES_TERMS:
+        t = d.get(name)
+        if type(t) is dict:
+            item = (name, tuple([(k, _tok(v, keep)) for k, v in t.items()]))
+            out = item if out is None else out + item
+    return out
+
+
 def _surface_token_py(s, keep, memo):
     geom = s.geometry
     im = getattr(s, "interaction_model", None)
+    terms = _forbes_terms(geom, keep)
     return (
         type(s).__name__, id(s),
         _obj(geom, keep, memo), _cs(getattr(geom, "cs", None), keep, memo),
@@ -224,11 +251,13 @@ def _surface_token_py(s, keep, memo):
         _obj(im, keep, memo, _SURFACE_SKIP),
         _coating(getattr(im, "coating", None), keep, memo),
         _tok(getattr(s, "thickness", None), keep), bool(getattr(s, "is_stop", False)),
-    )
+    ) + (() if terms is None else (terms,))
 
 
 def _surface_token_native(s, keep, memo):
-    return _NATIVE.surface_token(s, keep, memo, _SURFACE_SKIP)
+    tok = _NATIVE.surface_token(s, keep, memo, _SURFACE_SKIP)
+    terms = _forbes_terms(s.geometry, keep)
+    return tok if terms is None else tuple(tok) + (terms,)
 
 
 surface_token = _surface_token_native if _NATIVE is not None else _surface_token_py

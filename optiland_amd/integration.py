@@ -1105,14 +1105,20 @@ def _hip_surface_group_trace(group, rays, skip):
     (interactions/refractive_reflective_model.py:41) and PolarizedRays.p is advanced
     from its CURRENT value (rays/polarized_rays.py:180-202).
 
-    Surfaces the fused path does not implement (thin lens, grating, phase, Forbes / NURBS
+    Surfaces the fused path does not implement (thin lens, grating, phase, NURBS
     / grid-sag geometry, GRIN media, BSDF, thin-film coating ...) do not disqualify the
     whole system: they are traced by their own `Surface.trace(rays)` on the same device
     tensors, and the runs of supported surfaces between them are one launch each
     (`ol_trace`'s [first, last] range; SURVEY.md section 8b "split the system into supported
     segments").  A bundle a thin lens left un-normalised (`is_normalized == False`) takes
     one more reference surface, whose propagation renormalises it
-    (propagation/homogeneous.py:55-56)."""
+    (propagation/homogeneous.py:55-56).
+
+    Forbes surfaces (`table.forbes`: ForbesQNormalSlopeGeometry / ForbesQbfsGeometry /
+    ForbesQ2dGeometry) are device work too: inside a run they are one `ol_trace_forbes` launch
+    between two fused launches (`HipSystem.trace` splits the range), and they count as served
+    when the seam decides whether anything would run on the device at all.  A POLARISED bundle
+    takes the reference's own surface there, as before (that kernel is unpolarised)."""
     import optiland.backend as be
     from optiland.rays import PolarizedRays as RefPolarizedRays
     from optiland.rays import RealRays as RefRealRays
@@ -1135,6 +1141,8 @@ def _hip_surface_group_trace(group, rays, skip):
     if table is None:
         return None
     foreign = set(table.unsupported)
+    if polarized:
+        foreign |= set(table.forbes)
     if len(foreign) >= n_s - skip - (1 if skip == 0 else 0):
         return None  # nothing but the object row would run fused
     if table.uses_polarization and not polarized:

@@ -111,7 +111,121 @@ def cs_to_affine(cs):
     return R, t
 
 
-def _pack_geometry(geom, row, coeffs: list):
+def _forbes_classes():
+    """(ForbesQNormalSlopeGeometry, ForbesQ2dGeometry) of the reference, or None where it has
+    none.  Forbes surfaces are recognised by `isinstance` against these, never by name."""
+    try:
+        from optiland.geometries.forbes.geometry import (ForbesQ2dGeometry,
+                                                         ForbesQNormalSlopeGeometry)
+    except Exception:  # noqa: BLE001 - a reference without the Forbes family
+        return None
+    return ForbesQNormalSlopeGeometry, ForbesQ2dGeometry
+
+
+def _whole(v, what) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+        raise UnsupportedSystem(f"Forbes term index {v!r} ({what}) is not a whole number >= 0")
+    return int(v)
+
+
+def _forbes_pn_basis(cs: list) -> list:
+    """change_basis_qbfs_to_pn (geometries/forbes/qpoly.py:87-115) on Python floats, with the
+    reference's own recurrence constants f, g, h."""
+    from optiland.geometries.forbes import qpoly as Q
+
+    m = len(cs) - 1
+    if m < 0:
+        return []
+    bs = [0.0] * (m + 1)
+    bs[m] = cs[m] / Q.f_qbfs(m)
+    if m > 0:
+        bs[m - 1] = (cs[m - 1] - Q.g_qbfs(m - 1) * bs[m]) / Q.f_qbfs(m - 1)
+    for i in range(m - 2, -1, -1):
+        bs[i] = (cs[i] - Q.g_qbfs(i) * bs[i + 1] - Q.h_qbfs(i) * bs[i + 2]) / Q.f_qbfs(i)
+    return [float(b) for b in bs]
+
+
+def _forbes_q2d_quads(cns: list, m: int) -> list:
+    """One a- or b-list of azimuthal order m as the quads of OL_GEOM_FORBES_Q2D:
+    change_basis_q2d_to_pnm (qpoly.py:355-370) and, per n, the constants of the Clenshaw step
+    alpha_n = d_n + (A_n + B_n u^2) alpha_{n+1} - C_{n+1} alpha_{n+2} from the reference's
+    abc_q2d_clenshaw (qpoly.py:373-400, special cases and d == 0 -> 1e-99 included)."""
+    from optiland.geometries.forbes import qpoly as Q
+
+    n_max = len(cns) - 1
+    if n_max < 0:
+        return []
+    ds = [0.0] * (n_max + 1)
+    ds[n_max] = cns[n_max] / Q.f_q2d(n_max, m)
+    for n in range(n_max - 1, -1, -1):
+        ds[n] = (cns[n] - Q.g_q2d(n, m) * ds[n + 1]) / Q.f_q2d(n, m)
+    out = []
+    for n in range(n_max + 1):
+        a = b = c = 0.0
+        if n < n_max:
+            a, b, _ = Q.abc_q2d_clenshaw(n, m)
+        if n < n_max - 1:   # (the reference's sweep has no C term in its first two steps)
+            _, _, c = Q.abc_q2d_clenshaw(n + 1, m)
+        out.extend([float(ds[n]), float(a), float(b), float(c)])
+    return out
+
+
+def _pack_forbes(geom, row, coeffs: list, classes) -> None:
+    """A Forbes surface in full (tolerate mode only): base conic, solver settings, the CURRENT
+    normalisation radius and the term lists after the host-side basis change -- the blocks of
+    OL_GEOM_FORBES_Q / OL_GEOM_FORBES_Q2D (include/optiland_hip.h).  Raises `UnsupportedSystem`
+    for what stays with the reference's own surface."""
+    q_cls, q2d_cls = classes
+    if S.OPTIONS["reference_newton"]:
+        raise UnsupportedSystem("Forbes surface under the reference Newton rule")
+    row["radius"] = _f(geom.radius)
+    row["conic"] = _f(geom.k)
+    row["tol"] = float(geom.tol)
+    row["max_iter"] = int(geom.max_iter)
+    norm = _f(geom.norm_radius)
+    if not (math.isfinite(norm) and norm > 0.0):
+        raise UnsupportedSystem(f"Forbes norm_radius {norm!r}")
+    if _f(geom.radius) == 0.0 or math.isnan(_f(geom.radius)):
+        raise UnsupportedSystem("Forbes surface with a zero / NaN base radius")
+    row["norm_radius"] = norm
+    try:
+        if isinstance(geom, q2d_cls):
+            # what sag() and the normal READ: the lists _prepare_coeffs left behind
+            # (geometry.py:499-537) -- an edit of freeform_coeffs shows after that call, as in
+            # the reference's own trace
+            cm0 = [_f(v) for v in geom.cm0_coeffs]
+            ams = [[_f(v) for v in lst] for lst in geom.ams_coeffs]
+            bms = [[_f(v) for v in lst] for lst in geom.bms_coeffs]
+            for key in (geom.freeform_coeffs or {}):
+                kind, m_, n_ = key
+                if str(kind).lower() not in ("a", "b"):
+                    raise UnsupportedSystem(f"Forbes Q2D term key {key!r}")
+                _whole(m_, "m"), _whole(n_, "n")
+            big = max(len(ams), len(bms))
+            block = [float(len(cm0)), float(big)] + _forbes_pn_basis(cm0)
+            for i in range(big):
+                a = ams[i] if i < len(ams) else []
+                b = bms[i] if i < len(bms) else []
+                block += [float(len(a)), float(len(b))]
+                block += _forbes_q2d_quads(a, i + 1) + _forbes_q2d_quads(b, i + 1)
+            row["geom_kind"] = S.GEOM_FORBES_Q2D
+        else:
+            terms = geom.radial_terms or {}
+            keys = [_whole(k, "n") for k in terms]
+            cs = [_f(terms.get(n, 0.0)) for n in range(max(keys) + 1)] if keys else []
+            block = _forbes_pn_basis(cs)
+            row["geom_kind"] = S.GEOM_FORBES_Q
+    except UnsupportedSystem:
+        raise
+    except Exception as exc:  # noqa: BLE001 - a term dictionary this packer cannot read
+        raise UnsupportedSystem(f"Forbes terms not readable: {exc}") from exc
+    if not all(math.isfinite(v) for v in block):
+        raise UnsupportedSystem("Forbes terms are not finite")
+    row["n_coeff"] = len(block)
+    coeffs.extend(block)
+
+
+def _pack_geometry(geom, row, coeffs: list, forbes: bool = False):
     name = type(geom).__name__
     row["coeff_offset"] = len(coeffs)
     row["n_coeff"] = 0
@@ -199,6 +313,11 @@ def _pack_geometry(geom, row, coeffs: list):
         for c, (n, m) in zip(cj, z.indices):
             coeffs.extend([float(c), float(n), float(m), _f(z._norm_constant(n, m))])
         return
+    if forbes:
+        classes = _forbes_classes()
+        if classes is not None and isinstance(geom, classes):
+            _pack_forbes(geom, row, coeffs, classes)
+            return
     raise UnsupportedSystem(f"geometry {name} is not on the fused path")
 
 
@@ -325,9 +444,15 @@ def _scalar_index(material, w: float, which: str) -> float:
     return hit
 
 
-def _pack_surface_local(is_object: bool, surf, wl):
+def _is_forbes_row(row) -> bool:
+    return int(row["geom_kind"]) in (S.GEOM_FORBES_Q, S.GEOM_FORBES_Q2D)
+
+
+def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False):
     """One surface, packed by itself: (desc row, its coefficient block as a list with every
-    offset RELATIVE to the block, optics rows per wavelength).  Raises `UnsupportedSystem`."""
+    offset RELATIVE to the block, optics rows per wavelength).  Raises `UnsupportedSystem`.
+    forbes: a Forbes surface is packed as a row of its own kind (`pack_surfaces(tolerate=True)`)
+    instead of raising."""
     row = np.zeros((), dtype=S.SURFACE_DESC_DTYPE)
     opt = np.zeros(wl.size, dtype=S.SURFACE_OPTICS_DTYPE)
     coeffs: list = []
@@ -345,13 +470,15 @@ def _pack_surface_local(is_object: bool, surf, wl):
         )
     if getattr(im, "bsdf", None) is not None:
         raise UnsupportedSystem("BSDF scatter is not on the fused path")
-    _pack_geometry(geom, row, coeffs)
+    _pack_geometry(geom, row, coeffs, forbes and not is_object)
     if S.OPTIONS["reference_newton"] and int(row["geom_kind"]) not in (S.GEOM_PLANE,
                                                                       S.GEOM_STANDARD):
         # the reference's batch-global stop rule on this Newton-Raphson surface (opt-in)
         row["flags"] |= S.SURF_REFERENCE_NEWTON
     _pack_aperture(surf.aperture, row, coeffs)
     _pack_coating(surf.coating, row, coeffs)
+    if _is_forbes_row(row) and int(row["coating_kind"]) >= S.COAT_FRESNEL:
+        raise UnsupportedSystem("polarisation-dependent coating on a Forbes surface")
     if is_object:
         # ObjectSurface.trace only records (surfaces/object_surface.py:56-93)
         row["interaction"] = S.INTERACT_RECORD_ONLY
@@ -423,7 +550,11 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
     `tolerate`, packs a never-traced placeholder row for every such surface (except the
     object surface) and lists their indices in `table.unsupported`: the caller then
     launches the fused trace on the `[first, last]` runs between them and leaves those
-    surfaces to the reference (integration._hip_surface_group_trace).
+    surfaces to the reference (integration._hip_surface_group_trace).  With `tolerate` only, a
+    Forbes surface (the reference's ForbesQNormalSlopeGeometry / ForbesQbfsGeometry /
+    ForbesQ2dGeometry, by `isinstance`) is packed in full as a row of its own kind and listed in
+    `table.forbes`, not in `table.unsupported`: one `ol_trace_forbes` launch between two fused
+    runs (`HipSystem.trace`).  Strict packing keeps raising for it.
 
     `tokens` + `cache` (both or neither): per-surface change-detector tokens
     (fingerprint.surface_token, i.e. element [1] of `optic_token`) and a dict the caller
@@ -473,9 +604,11 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
             hit = cache.get(id(surf))
             if hit is not None and hit[0] == (tokens[i], i == 0, wl_key):
                 packed = hit[1]
+                if not tolerate and _is_forbes_row(packed[0]):   # (cached by a tolerant pack)
+                    raise UnsupportedSystem("Forbes geometry is not on the fused path")
         if packed is None:
             try:
-                packed = _pack_surface_local(i == 0, surf, wl)
+                packed = _pack_surface_local(i == 0, surf, wl, forbes=tolerate)
             except UnsupportedSystem:
                 if not tolerate or i == 0:
                     raise
@@ -504,7 +637,7 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
     )
     table.last_thickness = _f(surfaces[-1].thickness) if n_s else 0.0
     table.unsupported = tuple(unsupported)
-    if use_cache and not unsupported:
+    if use_cache and not unsupported and not table.forbes:
         cache["assembled"] = (tuple(id(s_) for s_ in surfaces), wl_key, list(tokens), bases,
                               table)
     return table

@@ -25,6 +25,8 @@ import numpy as np
 GEOM_PLANE, GEOM_STANDARD, GEOM_EVEN_ASPHERE, GEOM_ZERNIKE = 0, 1, 2, 3
 GEOM_ODD_ASPHERE, GEOM_POLYNOMIAL = 4, 5
 GEOM_CHEBYSHEV, GEOM_BICONIC, GEOM_TOROIDAL = 6, 7, 8
+# Forbes surfaces: one launch of their own each (ol_trace_forbes), never inside a fused range
+GEOM_FORBES_Q, GEOM_FORBES_Q2D = 9, 10
 INTERACT_RECORD_ONLY, INTERACT_REFRACT, INTERACT_REFLECT = 0, 1, 2
 AP_NONE, AP_RADIAL, AP_OFFSET_RADIAL, AP_RECTANGULAR, AP_ELLIPTICAL = 0, 1, 2, 3, 4
 AP_COMPOSITE = 5
@@ -55,6 +57,7 @@ TRACE_FEW_WAVES = 0x10  # the record block is an ordinary allocation (not a plac
 TRACE_PRT_COMPLEX = 0x4
 TRACE_PRT_IDENTITY = 0x8
 TRACE_NONUNIT_K = 0x20  # OL_TRACE_NONUNIT_K: polarised bundle whose directions are not unit
+TRACE_MIDRANGE = 0x40   # OL_TRACE_MIDRANGE (ol_trace_forbes): the trace goes on behind the surface
 
 GEOM_NAMES = {
     GEOM_PLANE: "plane",
@@ -66,6 +69,8 @@ GEOM_NAMES = {
     GEOM_CHEBYSHEV: "chebyshev",
     GEOM_BICONIC: "biconic",
     GEOM_TOROIDAL: "toroidal",
+    GEOM_FORBES_Q: "forbes_q",
+    GEOM_FORBES_Q2D: "forbes_q2d",
 }
 
 # numpy image of `ol_surface_desc`; align=True reproduces the C layout.
@@ -178,6 +183,18 @@ class SystemTable:
     def needs_complex_prt(self) -> bool:
         """Retarder coatings have a complex Jones matrix (jones.py:331-393)."""
         return bool(np.any(self.surfaces["coating_kind"] == COAT_RETARDER))
+
+    @property
+    def forbes(self) -> tuple:
+        """Indices of the Forbes rows (GEOM_FORBES_Q / GEOM_FORBES_Q2D): each is one
+        `ol_trace_forbes` launch between two fused runs (`HipSystem.trace` splits a range there).
+        Disjoint from `unsupported`, whose rows are placeholders nobody launches."""
+        memo = self.__dict__.get("_forbes")
+        if memo is None:
+            g = self.surfaces["geom_kind"]
+            memo = self.__dict__["_forbes"] = tuple(
+                int(i) for i in np.nonzero((g == GEOM_FORBES_Q) | (g == GEOM_FORBES_Q2D))[0])
+        return memo
 
     def reference_newton_surfaces(self, first: int = 0, last: int | None = None) -> list:
         """Traced Newton-Raphson surfaces of [first, last] that carry SURF_REFERENCE_NEWTON (the

@@ -1,0 +1,312 @@
+"""What the Forbes-surface tests share (tests/test_forbes_cpu.py, tests/test_gpu_forbes.py) and
+what tools/make_golden_forbes.py builds its fixture from: the singlet and its variants, the
+fixture tests/golden/forbes.npz, the bounds derived from it, the case files of tests/hostforbes
+and the CPU stand-in engine of the drop-in test.
+
+Bounds (one rule everywhere).
+  * tight cases (solver tol 1e-12) and the sag / normal grids: per recorded array -- (row, plane)
+    of a case, (quantity) of a grid -- three times the larger of the fixture's NumPy-to-torch
+    spread and its tol-1e-12-vs-1e-14 gap, with the floor 1e-12 (fp64), the agreement the README
+    states for conic systems;
+  * default-tolerance cases (1e-6): the project's contract, 1e-6 fp64 and 1e-4 fp32 -- the
+    reference stops batch-wide at max |f| < tol, the device converges further;
+  * fp32: the contract only;
+  * rays whose reference hit on a Q2D surface has |u - 1| < 1e-3 are left out (the Q2D sag jumps at
+    u = 1 when m > 0 terms are present); the generator asserts they are at most 2 % of a case;
+  * a ray that is NaN in the reference is NaN here, and no other.
+"""
+
+from __future__ import annotations
+
+import functools
+import importlib.util
+import os
+import subprocess
+
+import numpy as np
+
+from optiland_amd import system as S
+from optiland_amd.system import SystemTable
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLD = os.path.join(HERE, "golden", "forbes.npz")
+MAGIC = int.from_bytes(b"olFRBS", "little")
+
+WAVELENGTH = 0.55
+FORBES = 1                     # index of the Forbes surface in every variant
+TIGHT, DEFAULT, TIGHTER = 1e-12, 1e-6, 1e-14
+FLOOR = 1e-12
+CONTRACT = {np.float64: 1e-6, np.float32: 1e-4}
+EDGE = 1e-3                    # |u - 1| of the exclusion
+EDGE_CAP = 0.02
+
+Q_TERMS = {0: 2e-3, 1: -5e-4, 2: 1e-4, 3: 2e-5, 4: -1e-5}
+Q2D_TERMS = {
+    ("a", 0, 0): 2e-3, ("a", 0, 1): -5e-4, ("a", 0, 2): 1e-4,
+    ("a", 1, 0): 1e-3, ("b", 1, 0): -8e-4,
+    ("a", 1, 1): 4e-4, ("a", 1, 2): -2e-4, ("a", 1, 3): 1e-4,
+    ("a", 2, 0): 6e-4, ("b", 2, 1): 3e-4, ("a", 3, 1): 2e-5,
+}
+KINDS = ("q", "q2d")
+VARIANTS = ("norm12", "norm8", "tilted", "mirror", "flat", "clipped")
+RAYSETS = ("hex127", "chief")          # every case
+BIG_SET = "disc1027"                   # the norm8 case of each geometry only (file size)
+
+
+# ------------------------------------------------------------------ the lens (needs the reference)
+def singlet(kind: str, variant: str, tol: float = DEFAULT):
+    """R 40, k -0.5, N-BK7, stop on the Forbes surface, back radius -120, image 70 behind it, EPD
+    18, fields 0 / 5 degrees, 0.55 um -- and its variants.  Built on the ACTIVE backend of the
+    reference."""
+    import optiland.backend as be
+    from optiland import optic as optic_mod
+    from optiland.physical_apertures import RadialAperture
+
+    lens = optic_mod.Optic(name=f"forbes_{kind}_{variant}")
+    lens.surfaces.add(index=0, radius=be.inf, thickness=be.inf)
+    kw = dict(index=1, radius=be.inf if variant == "flat" else 40.0, conic=-0.5, thickness=6.0,
+              material="N-BK7", is_stop=True, tol=tol, max_iter=100,
+              norm_radius=8.0 if variant == "norm8" else 12.0)
+    if kind == "q":
+        kw.update(surface_type="forbes_qbfs", radial_terms=dict(Q_TERMS))
+    else:
+        kw.update(surface_type="forbes_q2d", freeform_coeffs=dict(Q2D_TERMS))
+    if variant == "tilted":
+        kw.update(rx=0.03, dy=0.4)
+    if variant == "clipped":
+        kw.update(aperture=RadialAperture(r_max=7.0))
+    if variant == "mirror":
+        kw.update(material="mirror", thickness=-20.0)
+        lens.surfaces.add(**kw)
+        lens.surfaces.add(index=2, radius=be.inf, thickness=-30.0)
+    else:
+        lens.surfaces.add(**kw)
+        lens.surfaces.add(index=2, radius=-120.0, thickness=70.0)
+    lens.surfaces.add(index=3)
+    lens.set_aperture(aperture_type="EPD", value=18.0)
+    lens.fields.set_type(field_type="angle")
+    lens.fields.add(y=0.0)
+    lens.fields.add(y=5.0)
+    lens.wavelengths.add(value=WAVELENGTH, is_primary=True)
+    return lens
+
+
+def pupil_points(rayset: str):
+    """(Hy, Px, Py) of a ray set: the field's 6-ring hexapolar pupil (127 rays: one full and one
+    partial wave), 1027 points uniform over the disc at Hy = 0.5, the on-axis chief ray alone."""
+    if rayset == "chief":
+        return 0.0, np.zeros(1), np.zeros(1)
+    if rayset == "hex127":
+        px, py = [0.0], [0.0]
+        for ring in range(1, 7):
+            th = 2.0 * np.pi * np.arange(6 * ring) / (6 * ring)
+            px.extend((ring / 6.0) * np.cos(th))
+            py.extend((ring / 6.0) * np.sin(th))
+        return 1.0, np.array(px), np.array(py)
+    rng = np.random.default_rng(1027)
+    r, th = np.sqrt(rng.uniform(0.0, 1.0, 1027)), rng.uniform(0.0, 2.0 * np.pi, 1027)
+    return 0.5, r * np.cos(th), r * np.sin(th)
+
+
+def packed(lens) -> SystemTable:
+    """The tolerant pack the drop-in's bridge makes of the lens' surfaces."""
+    from optiland_amd.packer import pack_surfaces
+
+    return pack_surfaces(lens.surfaces.surfaces, [WAVELENGTH], name=lens.name, tolerate=True)
+
+
+# ------------------------------------------------------------------ the fixture
+@functools.lru_cache(maxsize=None)
+def golden():
+    with np.load(GOLD) as z:
+        return {k: z[k] for k in z.files}
+
+
+def case_names():
+    return [str(c) for c in golden()["cases"]]
+
+
+@functools.lru_cache(maxsize=None)
+def case(name: str) -> dict:
+    """One case: kind, variant, tol, `table`, `rows` (S + 1, 8, n) of the reference (NumPy), its
+    per-array `spread` (NumPy to torch) and `gap` (tol 1e-12 to 1e-14) (S + 1, 8), the slices of
+    the ray sets and `edge` (n,): rays of the exclusion."""
+    g = golden()
+    out = {k.split("/", 1)[1]: g[k] for k in g if k.startswith(name + "/")}
+    out["name"] = name
+    out["kind"], out["variant"] = str(out["kind"]), str(out["variant"])
+    out["tol"] = float(out["tol"])
+    out["table"] = SystemTable.from_json(str(out["table"]))
+    if "delta" in out:   # a default-tolerance case is stored as its difference to the tight one
+        out["rows"] = case(str(out["tight"]))["rows"] + out.pop("delta").astype(np.float64)
+    out["sets"] = {str(k): (int(a), int(b)) for k, a, b in
+                   zip(out.pop("set_names"), out.pop("set_lo"), out.pop("set_hi"))}
+    out["edge"] = near_edge(out["table"], out["rows"]) if out["kind"] == "q2d" \
+        else np.zeros(out["rows"].shape[2], dtype=bool)
+    return out
+
+
+def local_hit(table: SystemTable, rows: np.ndarray):
+    """The recorded hit on the Forbes surface in that surface's own frame, (3, n)."""
+    row = table.surfaces[FORBES]
+    R = np.asarray(row["rot"], dtype=np.float64).reshape(3, 3)
+    return R @ (rows[FORBES, :3] - np.asarray(row["origin"], dtype=np.float64)[:, None])
+
+
+def near_edge(table: SystemTable, rows: np.ndarray) -> np.ndarray:
+    """Rays whose reference hit has |u - 1| < 1e-3 (NaN hits are not among them)."""
+    p = local_hit(table, rows)
+    u = np.hypot(p[0], p[1]) / float(table.surfaces[FORBES]["norm_radius"])
+    with np.errstate(invalid="ignore"):
+        return np.abs(u - 1.0) < EDGE
+
+
+def bound(c: dict, dtype=np.float64) -> np.ndarray:
+    """(S + 1, 8, 1): the bound of every recorded array of the case."""
+    if dtype is np.float32 or c["tol"] > TIGHT:
+        return np.full(c["rows"].shape[:2] + (1,), CONTRACT[dtype])
+    return np.maximum(3.0 * np.maximum(c["spread"], c["gap"]), FLOOR)[:, :, None]
+
+
+def grid_bound(g: dict, key: str) -> float:
+    return max(3.0 * float(g[key + "_spread"]), FLOOR)
+
+
+def grid(kind: str, variant: str) -> dict:
+    gd = golden()
+    pre = f"grid_{kind}_{variant}/"
+    out = {k[len(pre):]: gd[k] for k in gd if k.startswith(pre)}
+    out["table"] = SystemTable.from_json(str(out["table"]))
+    return out
+
+
+def compare(got: np.ndarray, c: dict, dtype=np.float64, lo: int = 0, hi: int | None = None,
+            rows=None, report=None) -> None:
+    """`got` (rows, 8, n) against the case's reference rows [lo:hi]: the NaN pattern, then every
+    array within its bound (edge rays of a Q2D case left out).  `rows`: the recorded surfaces
+    `got` holds (default: all)."""
+    want = c["rows"][:, :, lo:hi] if rows is None else c["rows"][rows][:, :, lo:hi]
+    lim = bound(c, dtype) if rows is None else bound(c, dtype)[rows]
+    assert got.shape == want.shape, (got.shape, want.shape)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), f"{c['name']}: NaN pattern differs"
+    keep = ~c["edge"][lo:hi]
+    with np.errstate(invalid="ignore"):
+        err = np.abs(got - want)[:, :, keep]
+    err = np.where(np.isnan(err), 0.0, err)
+    worst = err.max(axis=2, keepdims=True) if err.shape[2] else np.zeros(lim.shape)
+    if report is not None:
+        report(f"{c['name']} [{lo}:{hi}] {np.dtype(dtype).name}: worst error / bound = "
+               f"{float((worst / lim).max()):.3g} (worst error {float(worst.max()):.3g})")
+    assert np.all(worst <= lim), (c["name"], float((worst / lim).max()), worst[..., 0].tolist())
+
+
+# ------------------------------------------------------------------ tests/hostforbes
+def _builder():
+    spec = importlib.util.spec_from_file_location(
+        "_hostforbes_build", os.path.join(HERE, "hostforbes", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def write_case(path, table: SystemTable, planes, surface: int = FORBES, fp64: bool = True) -> None:
+    """The flat file tests/hostforbes/main.hip reads (its header comment has the layout)."""
+    surf = np.ascontiguousarray(table.surfaces)
+    optics = np.ascontiguousarray(table.optics)
+    coeffs = np.ascontiguousarray(table.coeffs, dtype=np.float64)
+    planes = np.ascontiguousarray(planes, dtype="<f8")
+    assert planes.shape[0] == 8
+    head = np.array([MAGIC, surf.shape[0], optics.shape[1], coeffs.size, planes.shape[1], surface,
+                     0, int(fp64)], dtype="<i8")
+    with open(path, "wb") as f:
+        for a in (head, surf, optics, coeffs, planes):
+            f.write(np.ascontiguousarray(a).tobytes())
+
+
+def run_host(exe: str, mode: str, path) -> str:
+    done = subprocess.run([exe, mode, str(path)], capture_output=True, text=True, timeout=120)
+    assert done.returncode == 0, (done.returncode, done.stdout[-400:], done.stderr[-400:])
+    return done.stdout
+
+
+def host_step(exe: str, path) -> np.ndarray:
+    """(8, n) of `hostforbes step`, and the OR of the rays' status bits."""
+    out, bits = [], 0
+    for line in run_host(exe, "step", path).splitlines():
+        part = line.split()
+        assert part[0] == "ray", line
+        out.append([float(v) for v in part[2:10]])
+        bits |= int(part[10])
+    return np.array(out, dtype=np.float64).reshape(-1, 8).T.copy(), bits
+
+
+def host_grid(exe: str, path) -> np.ndarray:
+    """(4, n) of `hostforbes grid`: sag, nx, ny, nz."""
+    out = []
+    for line in run_host(exe, "grid", path).splitlines():
+        part = line.split()
+        assert part[0] == "pt", line
+        out.append([float(v) for v in part[2:6]])
+    return np.array(out, dtype=np.float64).reshape(-1, 4).T.copy()
+
+
+# ------------------------------------------------------------------ CPU stand-in of the engine
+def make_engine_class(exe: str, tmp_dir):
+    """`OracleEngine` (tests/_fake_engine.py) for the fused runs + the host harness for the Forbes
+    rows, joined by the product's own splitter (`optiland_amd.engine.split_trace`): what
+    `HipSystem.trace` does on a range with Forbes rows, on CPU tensors."""
+    import torch
+
+    from optiland_amd.engine import PLANES, TraceResult, split_trace
+    from tests._fake_engine import OracleEngine
+
+    class ForbesOracleEngine(OracleEngine):
+        forbes_launches = 0
+
+        def trace_forbes(self, rays, surface, wavelength_index=0, record_row=None,
+                         write_rays=None, midrange=False, **_):
+            type(self).forbes_launches += 1
+            n = int(rays[0].numel())
+            path = os.path.join(str(tmp_dir), f"engine_{id(self)}.case")
+            write_case(path, self.table, np.stack([t.double().numpy() for t in rays]),
+                       surface=int(surface))
+            got, _bits = host_step(exe, path)
+            new = torch.as_tensor(got, dtype=rays[0].dtype)
+            if record_row is not None:
+                record_row[:, :n].copy_(new)
+            if write_rays or (write_rays is None and record_row is None):
+                for k in range(8):
+                    rays[k].copy_(new[k])
+            return 0
+
+        def trace(self, rays, wavelength_index=0, record=True, prt=None, first=0, last=None,
+                  write_rays=None, check_status=True, prt_identity=False,
+                  nonunit_directions=False):
+            last = self.num_surfaces - 1 if last is None else last
+            if not any(first <= f <= last for f in self.table.forbes):
+                return super().trace(rays, wavelength_index, record, prt, first, last, write_rays,
+                                     check_status, prt_identity, nonunit_directions)
+            assert prt is None, "the bridge keeps polarised bundles off the Forbes kernel"
+            rays = list(rays)
+            n = int(rays[0].numel())
+            rec = record if isinstance(record, torch.Tensor) else (
+                self.alloc_record(n, rays[0].dtype, last - first + 1) if record is True else None)
+            if write_rays is None:
+                write_rays = rec is None
+            work = rays if write_rays else [t.clone() for t in rays]
+            base = super()
+
+            def fused(a, b, view, r0, midrange):
+                assert r0 is None or r0 == a
+                base.trace(work, wavelength_index, record=view if view is not None else False,
+                           first=a, last=b, write_rays=True)
+
+            def one(s, row, midrange):
+                self.trace_forbes(work, s, wavelength_index, record_row=row, write_rays=True,
+                                  midrange=midrange)
+
+            split_trace(self.table.forbes, first, last, rec, first, fused, one)
+            return TraceResult(n, rays, rec, None, 0, first, last)
+
+    assert PLANES[0] == "x"
+    return ForbesOracleEngine

@@ -1,0 +1,227 @@
+// main.hip -- TEST INFRASTRUCTURE: the Forbes surface step of optiland_amd/csrc/forbes_device.h,
+// compiled for the host (OL_HOST_MATH) and run ray by ray as a stand-alone program.
+//
+//   hostforbes step <case file>     forbes_trace_kernel's body for every ray: one line per ray
+//   hostforbes grid <case file>     sag and unit normal at the points (planes 0 and 1)
+//   hostforbes refuse <case file>   every range-walking entry point on the case's system: one
+//                                   line per call with its return code (no launch happens)
+//   hostforbes create <case file>   ol_system_create alone: its return code and message
+//
+// Linked with the host-only compile of csrc/capi.hip (ol_system_create builds the table the
+// kernel reads) and tests/hostmath/harness.hip (the stand-in for the few HIP runtime calls
+// capi.hip makes) -- the objects tests/hostmath/build.py leaves behind, plain or with
+// AddressSanitizer + UndefinedBehaviorSanitizer.  A program of its own: nothing is loaded into
+// an interpreter.  Not a fallback: nothing under optiland_amd/ knows about it.
+//
+// Case file (little endian): 8 int64 -- magic, n_surf, n_wl, n_coeff, n, surface, wavelength
+// index, dtype (0 = fp32, 1 = fp64); then n_surf ol_surface_desc, n_surf x n_wl
+// ol_surface_optics, n_coeff doubles, 8 planes of n doubles (x, y, z, L, M, N, i, opd).
+#define OL_HOST_MATH 1
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/optiland_hip.h"
+#include "../../optiland_amd/csrc/forbes_device.h"
+#include "../../optiland_amd/csrc/ray_aim_host.h"
+#include "../../optiland_amd/csrc/system_view.h"
+
+namespace {
+
+constexpr int64_t kMagic = 0x534252466c6fLL;   // "olFRBS"
+
+struct Case {
+  int64_t h[8];
+  std::vector<ol_surface_desc> surf;
+  std::vector<ol_surface_optics> optics;
+  std::vector<double> coeffs, plane[8];
+};
+
+bool read_exact(FILE* f, void* dst, size_t bytes) { return bytes == 0 || fread(dst, bytes, 1, f) == 1; }
+
+bool load(const char* path, Case& c) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  bool ok = read_exact(f, c.h, sizeof c.h) && c.h[0] == kMagic;
+  // sizes a case file of this suite stays far inside: a corrupt header must not allocate
+  ok = ok && c.h[1] > 0 && c.h[1] < 4096 && c.h[2] > 0 && c.h[2] < 64 && c.h[3] >= 0 &&
+       c.h[3] < (1 << 24) && c.h[4] >= 0 && c.h[4] < (1 << 24);
+  if (ok) {
+    const size_t ns = (size_t)c.h[1], nw = (size_t)c.h[2], nc = (size_t)c.h[3], n = (size_t)c.h[4];
+    c.surf.resize(ns);
+    c.optics.resize(ns * nw);
+    c.coeffs.resize(nc);
+    ok = read_exact(f, c.surf.data(), ns * sizeof(ol_surface_desc)) &&
+         read_exact(f, c.optics.data(), ns * nw * sizeof(ol_surface_optics)) &&
+         read_exact(f, c.coeffs.data(), nc * sizeof(double));
+    for (auto& p : c.plane) {
+      p.resize(n);
+      ok = ok && read_exact(f, p.data(), n * sizeof(double));
+    }
+  }
+  fclose(f);
+  return ok;
+}
+
+template <typename T>
+struct Rows {
+  const ol::DevSurfHot<T>* hot;
+  const ol::DevSurfCold<T>* cold;
+  const ol::DevOptics<T>* opt;
+  const T* coeffs;
+};
+template <typename T>
+Rows<T> rows_of(const ol::SystemView& v);
+template <>
+Rows<double> rows_of<double>(const ol::SystemView& v) { return {v.surf, v.cold, v.optics, v.coeffs}; }
+template <>
+Rows<float> rows_of<float>(const ol::SystemView& v) {
+  return {v.surf32, v.cold32, v.optics32, v.coeffs32};
+}
+
+bool forbes_row(const Case& c, const ol::SystemView& v) {
+  const int64_t s = c.h[5];
+  if (s < 0 || s >= v.n_surf || !ol::is_forbes_kind(v.geom[s]) || c.h[6] < 0 || c.h[6] >= v.n_wl) {
+    printf("error: surface %lld is not a Forbes row of the case / bad wavelength index\n",
+           (long long)s);
+    return false;
+  }
+  return true;
+}
+
+// forbes_trace_kernel (forbes.hip) for ray i, statement by statement: a "wave" of one ray
+template <typename T>
+int step(const Case& c, const ol::SystemView& v) {
+  using namespace ol;
+  if (!forbes_row(c, v)) return 1;
+  const Rows<T> t = rows_of<T>(v);
+  const int64_t s = c.h[5];
+  const SurfFetched<T> h{as_const(t.hot + s), as_const(t.cold + s),
+                         as_const(t.opt + (s * v.n_wl + c.h[6]))};
+  for (int64_t i = 0; i < c.h[4]; ++i) {
+    Ray<T> r;
+    r.x = (T)c.plane[0][i]; r.y = (T)c.plane[1][i]; r.z = (T)c.plane[2][i];
+    r.L = (T)c.plane[3][i]; r.M = (T)c.plane[4][i]; r.N = (T)c.plane[5][i];
+    r.i = (T)c.plane[6][i]; r.opd = (T)c.plane[7][i];
+    const Ray<T> g = forbes_step<T>(h, as_const(t.coeffs), r);
+    const uint32_t bits = (g.L != g.L && g.x == g.x) ? OL_STATUS_NAN_DIRECTION : 0u;
+    printf("ray %lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %u\n", (long long)i,
+           (double)g.x, (double)g.y, (double)g.z, (double)g.L, (double)g.M, (double)g.N,
+           (double)g.i, (double)g.opd, bits);
+  }
+  return 0;
+}
+
+// geometry.sag(x, y) and geometry._surface_normal(x, y) (geometry.py:288-309, 573-594)
+template <typename T>
+int grid(const Case& c, const ol::SystemView& v) {
+  using namespace ol;
+  if (!forbes_row(c, v)) return 1;
+  const Rows<T> t = rows_of<T>(v);
+  const int64_t s = c.h[5];
+  const SurfFetched<T> h{as_const(t.hot + s), as_const(t.cold + s),
+                         as_const(t.opt + (s * v.n_wl + c.h[6]))};
+  for (int64_t i = 0; i < c.h[4]; ++i) {
+    const DevSurf<T> S = h.surf();
+    T sag, fx, fy;
+    forbes_eval<T>(S, as_const(t.coeffs) + S.coeff_off, (T)c.plane[0][i], (T)c.plane[1][i], sag, fx,
+                   fy);
+    const double mag = std::sqrt((double)fx * fx + (double)fy * fy + 1.0);
+    printf("pt %lld %.17g %.17g %.17g %.17g\n", (long long)i, (double)sag, fx / mag, fy / mag,
+           -1.0 / mag);
+  }
+  return 0;
+}
+
+// every entry point that walks a surface range, on a range that holds the case's Forbes row:
+// OL_EUNSUPPORTED before anything is launched (the arguments behind the range are never read)
+int refuse(const Case& c, ol_system* sys) {
+  const int32_t last = (int32_t)c.h[1] - 1, wl = (int32_t)c.h[6], s = (int32_t)c.h[5];
+  double plane[4] = {0, 0, 0, 0};
+  void* rays[8] = {plane, plane, plane, plane, plane, plane, plane, plane};
+  uint32_t status = 0;
+  int32_t iters[8192] = {0};
+  ol_raygen_params rg{};
+  ol_raygen_inputs in{};
+  in.px = plane;
+  in.py = plane;
+  auto say = [](const char* what, int rc) {
+    printf("%s: %d %s\n", what, rc, rc ? ol_last_error() : "ok");
+  };
+  say("ol_trace", ol_trace(sys, OL_F64, 1, rays, wl, nullptr, 0, nullptr, 0, last,
+                           OL_TRACE_WRITE_RAYS, &status, nullptr));
+  say("ol_trace one surface", ol_trace(sys, OL_F32, 1, rays, wl, nullptr, 0, nullptr, s, s,
+                                       OL_TRACE_WRITE_RAYS, &status, nullptr));
+  say("ol_trace_ex", ol_trace_ex(sys, OL_F64, 1, rays, wl, nullptr, 0, nullptr, 0, last,
+                                 OL_TRACE_WRITE_RAYS, &status, nullptr, nullptr));
+  say("ol_trace before the row", s > 1 ? ol_trace(sys, OL_F64, 1, rays, wl, nullptr, 0, nullptr, 0,
+                                                  s - 1, OL_TRACE_WRITE_RAYS, &status, nullptr)
+                                       : 0);
+  say("ol_newton_count", ol_newton_count(sys, OL_F64, 1, rays, wl, 0, last, iters, 0, nullptr));
+  say("ol_trace_generate", ol_trace_generate(sys, OL_F64, 1, &rg, &in, wl, plane, 1, nullptr,
+                                             nullptr, 0, &status, nullptr, nullptr));
+  void* hits[3] = {plane, plane, plane};
+  double out8[8] = {0};
+  say("ol_trace_spot", ol_trace_spot(sys, OL_F64, 1, &rg, &in, 0.0, 0.0, wl, hits, out8, &status,
+                                     nullptr));
+  ol_spot_cell cell{};
+  cell.wavelength_index = wl;
+  say("ol_trace_spot_batch", ol_trace_spot_batch(sys, OL_F64, 1, &rg, &in, 1, &cell, nullptr, 0,
+                                                 out8, &status, nullptr));
+  ol_wavefront_params wp{};
+  double mom[OL_WAVEFRONT_REFERENCE_DOUBLES + 16] = {0};
+  void* opd_out[3] = {plane, plane, plane};
+  say("ol_trace_opd", ol_trace_opd(sys, OL_F64, 1, &rg, &in, &wp, wl, plane, plane, opd_out, mom,
+                                   &status, nullptr));
+  say("ol_wavefront_reference", ol_wavefront_reference(sys, OL_F64, &rg, &in, &wp, 0.0, 0, wl, mom,
+                                                       mom, &status, nullptr));
+  say("ol_trace_opd_dev", ol_trace_opd_dev(sys, OL_F64, 1, &rg, &in, mom, wl, plane, plane,
+                                           opd_out, mom, &status, nullptr));
+  ol_aim_params ap{};
+  ap.max_iter = 1;
+  void* aim_out[6] = {plane, plane, plane, plane, plane, plane};
+  say("ol_aim_rays", ol::aim_check(sys, 1, wl, 0, last, &ap, &in, nullptr, aim_out, &status));
+  return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  const char* modes[] = {"step", "grid", "refuse", "create"};
+  int mode = -1;
+  for (int k = 0; k < 4 && argc == 3; ++k)
+    if (strcmp(argv[1], modes[k]) == 0) mode = k;
+  if (mode < 0) {
+    fprintf(stderr, "usage: hostforbes step|grid|refuse|create <case file>\n");
+    return 2;
+  }
+  Case c;
+  if (!load(argv[2], c)) {
+    fprintf(stderr, "hostforbes: cannot read the case file %s\n", argv[2]);
+    return 2;
+  }
+  ol_system* sys = nullptr;
+  const int rc = ol_system_create(c.surf.data(), (int32_t)c.surf.size(),
+                                  c.coeffs.empty() ? nullptr : c.coeffs.data(),
+                                  (int32_t)c.coeffs.size(), c.optics.data(), (int32_t)c.h[2], &sys);
+  if (mode == 3) {
+    printf("create: %d %s\n", rc, rc ? ol_last_error() : "ok");
+    ol_system_destroy(sys);
+    return 0;
+  }
+  if (rc != OL_OK) {
+    fprintf(stderr, "hostforbes: ol_system_create: %s\n", ol_last_error());
+    return 2;
+  }
+  const ol::SystemView v = ol::system_view(sys);
+  int out = 0;
+  if (mode == 0) out = c.h[7] ? step<double>(c, v) : step<float>(c, v);
+  if (mode == 1) out = c.h[7] ? grid<double>(c, v) : grid<float>(c, v);
+  if (mode == 2) out = refuse(c, sys);
+  ol_system_destroy(sys);
+  return out;
+}
