@@ -19,6 +19,7 @@
 
 #include "../../include/optiland_hip.h"
 #include "device_table.h"
+#include "entry_rules.h"
 #include "last_error.h"
 #include "system_view.h"
 #include "trace_launch.h"
@@ -39,7 +40,7 @@ int ol::failf(int code, const char* fmt, ...) {
 
 namespace {
 
-using ol::failf;
+using namespace ol;   // failf and the shared argument rules (entry_rules.h)
 
 #define OL_HIP_CHECK(expr)                                                        \
   do {                                                                            \
@@ -276,11 +277,6 @@ struct ol_system {
   bool consistent = true;
 };
 
-#define OL_CHECK_CONSISTENT(sys, who)                                                          \
-  if (!(sys)->consistent)                                                                      \
-    return failf(OL_EINVAL, who ": the system's tables are inconsistent after a failed "         \
-                                "ol_system_update (destroy it and create a new one)")
-
 namespace {
 
 // in_place: the allocation of `dst` is reused (it must fit: checked by the caller) and the
@@ -392,17 +388,6 @@ int newton_family(const ol_system* sys, int32_t first, int32_t last) {
   return 1;
 }
 
-// Forbes rows (OL_GEOM_FORBES_Q / _Q2D) are traced by ol_trace_forbes alone (forbes.hip): the
-// fused kernels carry no functor for them, so every entry point that walks a surface range
-// answers a range that holds one here, before any launch
-int refuse_forbes(const char* who, const ol_system* sys, int32_t first, int32_t last) {
-  for (int32_t s = first; s <= last; ++s)
-    if (ol::is_forbes_kind(sys->geom[s]))
-      return failf(OL_EUNSUPPORTED, "%s: surface %d is a Forbes surface: trace it with "
-                                    "ol_trace_forbes and cut the range there", who, s);
-  return OL_OK;
-}
-
 template <typename T>
 int do_trace(const ol_system* sys, const DeviceTable<T>& tab, int64_t n, void* const rays[8],
              int32_t wl, void* record, int64_t record_stride, void* prt, int32_t first,
@@ -461,16 +446,6 @@ int do_trace(const ol_system* sys, const DeviceTable<T>& tab, int64_t n, void* c
   hipError_t e = ol::launch_trace<T>(a, vec, family, stream);
   if (e != hipSuccess) return failf(OL_EHIP, "trace launch failed: %s", hipGetErrorString(e));
   return OL_OK;
-}
-
-// the fused entry points (one launch: generate -> trace [-> reduce]) do not serve ranges whose
-// Newton iteration count is a property of the batch
-int refuse_reference_newton(const char* who, const ol_system* sys) {
-  if (int rc = refuse_forbes(who, sys, 0, sys->n_surf - 1)) return rc;
-  if (newton_family(sys, 0, sys->n_surf - 1) != ol::kNrReference) return OL_OK;
-  return failf(OL_EUNSUPPORTED, "%s: the system carries OL_SURF_REFERENCE_NEWTON surfaces "
-                                "(reference stop rule): generate with ol_generate_rays, count "
-                                "with ol_newton_count, trace with ol_trace_ex", who);
 }
 
 // ol_raygen_inputs -> working precision; host-side part of the range validation
@@ -625,6 +600,17 @@ template <>
 const DeviceTable<float>& table_of<float>(const ol_system* sys) { return sys->f32; }
 template <>
 const DeviceTable<double>& table_of<double>(const ol_system* sys) { return sys->f64; }
+
+// f(T(0)) for the working type T of `dt` (OL_F32: float, else double: the entry has checked it);
+// with a system, f(T(0), the system's table of that precision)
+template <typename F>
+auto by_dtype(ol_dtype dt, F&& f) {
+  return dt == OL_F32 ? f(float(0)) : f(double(0));
+}
+template <typename F>
+int by_dtype(ol_dtype dt, const ol_system* sys, F&& f) {
+  return dt == OL_F32 ? f(float(0), sys->f32) : f(double(0), sys->f64);
+}
 
 template <typename T>
 int do_trace_spot_batch(const ol_system* sys, const DeviceTable<T>& tab, int64_t n,
@@ -1107,7 +1093,7 @@ int ol_system_create(const ol_surface_desc* surf, int32_t n_surf, const double* 
   sys->n_surf = n_surf;
   sys->n_wl = n_wavelengths;
   adopt_host_copies(sys, st);
-  if (hipGetDevice(&sys->device) != hipSuccess) {
+  if (!current_device(&sys->device)) {
     delete sys;
     return failf(OL_EHIP, "ol_system_create: no HIP device (hipGetDevice failed)");
   }
@@ -1135,17 +1121,12 @@ int ol_system_update(ol_system* sys, const ol_surface_desc* surf, int32_t n_surf
   if (int rc = stage_system("ol_system_update", surf, n_surf, coeffs, n_coeffs, optics,
                             n_wavelengths, st))
     return rc;
-  OL_CHECK_CONSISTENT(sys, "ol_system_update");
+  if (int rc = rule_consistent("ol_system_update", sys->consistent)) return rc;
   const size_t need = st.coeffs.size() ? st.coeffs.size() : 1;
   if (need > sys->f32.coef_capacity || need > sys->f64.coef_capacity)
     return failf(OL_EUNSUPPORTED, "ol_system_update: coefficient block of %zu values exceeds the "
                                   "allocated %zu", need, sys->f32.coef_capacity);
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return failf(OL_EINVAL, "ol_system_update: current HIP device %d is not the system's "
-                              "device %d", cur, sys->device);
-  }
+  if (int rc = rule_current_device("ol_system_update", system_view(sys))) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   // the fp64 table first: if its copy fails nothing has changed yet and the system stays
   // usable; only a failure of the SECOND copy leaves the two precisions apart
@@ -1180,30 +1161,18 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const r
                 int32_t wavelength_index, void* record, int64_t record_stride, void* prt,
                 int32_t first_surface, int32_t last_surface, uint32_t flags, uint32_t* status,
                 const ol_trace_extras* extras, void* stream) {
-  if (!sys) return failf(OL_EINVAL, "ol_trace: system is NULL");
-  OL_CHECK_CONSISTENT(sys, "ol_trace");
-  if (dt != OL_F32 && dt != OL_F64) return failf(OL_EINVAL, "ol_trace: bad dtype %d", (int)dt);
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace: negative ray count");
-  if (first_surface < 0 || last_surface >= sys->n_surf || first_surface > last_surface)
-    return failf(OL_EINVAL, "ol_trace: surface range [%d, %d] outside [0, %d)", first_surface,
-                 last_surface, sys->n_surf);
-  if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return failf(OL_EINVAL, "ol_trace: wavelength index %d outside [0, %d)", wavelength_index,
-                 sys->n_wl);
-  if (int rc = refuse_forbes("ol_trace", sys, first_surface, last_surface)) return rc;
+  SystemView v;
+  if (int rc = rule_system("ol_trace", sys, v)) return rc;
+  if (int rc = rule_dtype("ol_trace", dt)) return rc;
+  if (int rc = rule_count("ol_trace", n_rays, "negative ray count")) return rc;
+  if (int rc = rule_range("ol_trace", v, first_surface, last_surface)) return rc;
+  if (int rc = rule_wavelength("ol_trace", v.n_wl, wavelength_index)) return rc;
+  if (int rc = rule_no_forbes("ol_trace", v, first_surface, last_surface)) return rc;
   if (n_rays == 0) return OL_OK;
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return failf(OL_EINVAL, "ol_trace: current HIP device %d is not the system's device %d",
-                   cur, sys->device);
-  }
-  if (!rays) return failf(OL_EINVAL, "ol_trace: rays is NULL");
-  for (int k = 0; k < 8; ++k)
-    if (!rays[k]) return failf(OL_EINVAL, "ol_trace: rays[%d] is NULL", k);
-  if (record && record_stride < n_rays)
-    return failf(OL_EINVAL, "ol_trace: record_stride %lld < n_rays %lld", (long long)record_stride,
-                 (long long)n_rays);
+  if (int rc = rule_current_device("ol_trace", v)) return rc;
+  if (int rc = rule_planes("ol_trace", "rays", rays, 8)) return rc;
+  if (record)
+    if (int rc = rule_stride("ol_trace", record_stride, n_rays)) return rc;
   if (!record && !(flags & OL_TRACE_WRITE_RAYS) && !prt && !(extras && extras->spot_slots))
     return failf(OL_EINVAL, "ol_trace: nothing to write (no record, no OL_TRACE_WRITE_RAYS)");
   if (extras && extras->record_first_surface > last_surface)
@@ -1212,68 +1181,45 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const r
   if (prt && extras && extras->spot_slots)
     return failf(OL_EINVAL, "ol_trace_ex: the spot epilogue is for unpolarised traces (the "
                             "polarised intensity needs ol_polarized_intensity first)");
-  if (!prt) {
-    // rays/ray_generator.py:89-94: polarization-dependent coatings need polarized rays
-    for (int32_t s = first_surface; s <= last_surface; ++s)
-      if (sys->coating[s] >= OL_COAT_FRESNEL)
-        return failf(OL_EINVAL,
-                     "Polarization must be set when surfaces have polarization-dependent "
-                     "coatings.");
-  }
-  if (prt && !(flags & OL_TRACE_PRT_COMPLEX)) {
-    for (int32_t s = first_surface; s <= last_surface; ++s)
-      if (sys->coating[s] == OL_COAT_RETARDER)
-        return failf(OL_EINVAL, "ol_trace: surface %d is a retarder (complex Jones matrix): "
-                                "pass an 18-plane prt with OL_TRACE_PRT_COMPLEX", s);
-  }
+  if (!prt)
+    if (int rc = rule_polarisation_required(v, first_surface, last_surface)) return rc;
+  if (prt && !(flags & OL_TRACE_PRT_COMPLEX))
+    if (int rc = rule_retarder_needs_complex("ol_trace", v, first_surface, last_surface)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dt == OL_F32)
-    return do_trace<float>(sys, sys->f32, n_rays, rays, wavelength_index, record, record_stride,
-                           prt, first_surface, last_surface, flags, status, extras, st);
-  return do_trace<double>(sys, sys->f64, n_rays, rays, wavelength_index, record, record_stride,
-                          prt, first_surface, last_surface, flags, status, extras, st);
+  return by_dtype(dt, sys, [&](auto zero, const auto& table) {
+    return do_trace<decltype(zero)>(sys, table, n_rays, rays, wavelength_index, record,
+                                    record_stride, prt, first_surface, last_surface, flags, status,
+                                    extras, st);
+  });
 }
 
 int ol_newton_count(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const rays[8],
                     int32_t wavelength_index, int32_t first_surface, int32_t surface,
                     int32_t* iterations, int32_t verify, void* stream) {
-  if (!sys) return failf(OL_EINVAL, "ol_newton_count: system is NULL");
-  OL_CHECK_CONSISTENT(sys, "ol_newton_count");
-  if (dt != OL_F32 && dt != OL_F64)
-    return failf(OL_EINVAL, "ol_newton_count: bad dtype %d", (int)dt);
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_newton_count: negative ray count");
-  if (first_surface < 0 || surface >= sys->n_surf || first_surface > surface)
-    return failf(OL_EINVAL, "ol_newton_count: surface range [%d, %d] outside [0, %d)",
-                 first_surface, surface, sys->n_surf);
-  if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return failf(OL_EINVAL, "ol_newton_count: wavelength index %d outside [0, %d)",
-                 wavelength_index, sys->n_wl);
+  SystemView v;
+  if (int rc = rule_system("ol_newton_count", sys, v)) return rc;
+  if (int rc = rule_dtype("ol_newton_count", dt)) return rc;
+  if (int rc = rule_count("ol_newton_count", n_rays, "negative ray count")) return rc;
+  if (int rc = rule_range("ol_newton_count", v, first_surface, surface)) return rc;
+  if (int rc = rule_wavelength("ol_newton_count", v.n_wl, wavelength_index)) return rc;
   if (!iterations) return failf(OL_EINVAL, "ol_newton_count: iterations is NULL");
-  if (int rc = refuse_forbes("ol_newton_count", sys, first_surface, surface)) return rc;
-  if (!sys->ref_newton[surface])
+  if (int rc = rule_no_forbes("ol_newton_count", v, first_surface, surface)) return rc;
+  if (!v.ref_newton[surface])
     return failf(OL_EINVAL, "ol_newton_count: surface %d is not a traced Newton-Raphson surface "
                             "with OL_SURF_REFERENCE_NEWTON", surface);
   if (n_rays == 0) return OL_OK;
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return failf(OL_EINVAL, "ol_newton_count: current HIP device %d is not the system's "
-                              "device %d", cur, sys->device);
-  }
-  if (!rays) return failf(OL_EINVAL, "ol_newton_count: rays is NULL");
-  for (int k = 0; k < 8; ++k)
-    if (!rays[k]) return failf(OL_EINVAL, "ol_newton_count: rays[%d] is NULL", k);
+  if (int rc = rule_current_device("ol_newton_count", v)) return rc;
+  if (int rc = rule_planes("ol_newton_count", "rays", rays, 8)) return rc;
   // the geometry of a ray does not depend on its polarisation: the unpolarised kernel over
   // [first_surface, surface], nothing recorded, nothing written back
   ol_trace_extras ex{};
   ex.newton_iterations = iterations;
   ex.newton_count_surface = verify ? -1 : surface;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dt == OL_F32)
-    return do_trace<float>(sys, sys->f32, n_rays, rays, wavelength_index, nullptr, 0, nullptr,
-                           first_surface, surface, 0u, nullptr, &ex, st);
-  return do_trace<double>(sys, sys->f64, n_rays, rays, wavelength_index, nullptr, 0, nullptr,
-                          first_surface, surface, 0u, nullptr, &ex, st);
+  return by_dtype(dt, sys, [&](auto zero, const auto& table) {
+    return do_trace<decltype(zero)>(sys, table, n_rays, rays, wavelength_index, nullptr, 0,
+                                    nullptr, first_surface, surface, 0u, nullptr, &ex, st);
+  });
 }
 
 int ol_trace_generate(const ol_system* sys, ol_dtype dt, int64_t n_rays,
@@ -1281,16 +1227,13 @@ int ol_trace_generate(const ol_system* sys, ol_dtype dt, int64_t n_rays,
                       int32_t wavelength_index, void* record, int64_t record_stride,
                       void* const rays_out[8], void* prt, uint32_t flags, uint32_t* status,
                       const ol_trace_extras* extras, void* stream) {
-  if (!sys) return failf(OL_EINVAL, "ol_trace_generate: system is NULL");
-  OL_CHECK_CONSISTENT(sys, "ol_trace_generate");
-  if (int rc = refuse_reference_newton("ol_trace_generate", sys)) return rc;
-  if (dt != OL_F32 && dt != OL_F64)
-    return failf(OL_EINVAL, "ol_trace_generate: bad dtype %d", (int)dt);
+  SystemView v;
+  if (int rc = rule_system("ol_trace_generate", sys, v)) return rc;
+  if (int rc = rule_no_reference_newton("ol_trace_generate", v)) return rc;
+  if (int rc = rule_dtype("ol_trace_generate", dt)) return rc;
   if (!p || !in) return failf(OL_EINVAL, "ol_trace_generate: NULL argument");
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_generate: negative ray count");
-  if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return failf(OL_EINVAL, "ol_trace_generate: wavelength index %d outside [0, %d)",
-                 wavelength_index, sys->n_wl);
+  if (int rc = rule_count("ol_trace_generate", n_rays, "negative ray count")) return rc;
+  if (int rc = rule_wavelength("ol_trace_generate", v.n_wl, wavelength_index)) return rc;
   if ((in->vx || in->vy) && !(in->hx && in->hy))
     return failf(OL_EUNSUPPORTED, "ol_trace_generate: per-ray vignetting planes come with "
                                   "per-ray field planes (else ol_generate_rays + ol_trace)");
@@ -1307,101 +1250,74 @@ int ol_trace_generate(const ol_system* sys, ol_dtype dt, int64_t n_rays,
                               "cannot be combined");
   }
   if (!record) return failf(OL_EINVAL, "ol_trace_generate: record is NULL");
-  if (record_stride < n_rays)
-    return failf(OL_EINVAL, "ol_trace_generate: record_stride %lld < n_rays %lld",
-                 (long long)record_stride, (long long)n_rays);
+  if (int rc = rule_stride("ol_trace_generate", record_stride, n_rays)) return rc;
   if (extras && extras->record_first_surface >= sys->n_surf)
     return failf(OL_EINVAL, "ol_trace_generate: record_first_surface %d outside [0, %d)",
                  extras->record_first_surface, sys->n_surf);
   if (rays_out)
-    for (int k = 0; k < 8; ++k)
-      if (!rays_out[k]) return failf(OL_EINVAL, "ol_trace_generate: rays_out[%d] is NULL", k);
-  if (!prt) {
-    for (int32_t s = 0; s < sys->n_surf; ++s)
-      if (sys->coating[s] >= OL_COAT_FRESNEL)
-        return failf(OL_EINVAL,
-                     "Polarization must be set when surfaces have polarization-dependent "
-                     "coatings.");
-  }
-  if (prt && !(flags & OL_TRACE_PRT_COMPLEX)) {
-    for (int32_t s = 0; s < sys->n_surf; ++s)
-      if (sys->coating[s] == OL_COAT_RETARDER)
-        return failf(OL_EINVAL, "ol_trace_generate: surface %d is a retarder (complex Jones "
-                                "matrix): pass an 18-plane prt with OL_TRACE_PRT_COMPLEX", s);
-  }
-  if (n_rays > 0) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return failf(OL_EINVAL, "ol_trace_generate: current HIP device %d is not the system's "
-                              "device %d", cur, sys->device);
-  }
+    if (int rc = rule_planes("ol_trace_generate", "rays_out", rays_out, 8)) return rc;
+  if (!prt)
+    if (int rc = rule_polarisation_required(v, 0, v.n_surf - 1)) return rc;
+  if (prt && !(flags & OL_TRACE_PRT_COMPLEX))
+    if (int rc = rule_retarder_needs_complex("ol_trace_generate", v, 0, v.n_surf - 1)) return rc;
+  if (n_rays > 0)
+    if (int rc = rule_current_device("ol_trace_generate", v)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dt == OL_F32)
-    return do_trace_generate<float>(sys, sys->f32, n_rays, p, in, wavelength_index, record,
-                                    record_stride, rays_out, prt, flags, status, extras, st);
-  return do_trace_generate<double>(sys, sys->f64, n_rays, p, in, wavelength_index, record,
-                                   record_stride, rays_out, prt, flags, status, extras, st);
+  return by_dtype(dt, sys, [&](auto zero, const auto& table) {
+    return do_trace_generate<decltype(zero)>(sys, table, n_rays, p, in, wavelength_index, record,
+                                             record_stride, rays_out, prt, flags, status, extras,
+                                             st);
+  });
 }
 
 int ol_generate_rays(const ol_raygen_params* p, ol_dtype dt, int64_t n,
                      const ol_raygen_inputs* in, void* const out[8], uint32_t* status,
                      void* stream) {
   if (!p || !in || !out) return failf(OL_EINVAL, "ol_generate_rays: NULL argument");
-  if (n < 0) return failf(OL_EINVAL, "ol_generate_rays: negative count");
-  for (int k = 0; k < 7; ++k)
-    if (!out[k] && n > 0) return failf(OL_EINVAL, "ol_generate_rays: out[%d] is NULL", k);
+  if (int rc = rule_count("ol_generate_rays", n, "negative count")) return rc;
+  if (n > 0)
+    if (int rc = rule_planes("ol_generate_rays", "out", out, 7)) return rc;
+  if (int rc = rule_dtype("ol_generate_rays", dt)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dt == OL_F32) return do_generate_rays<float>(p, n, in, out, status, st);
-  if (dt == OL_F64) return do_generate_rays<double>(p, n, in, out, status, st);
-  return failf(OL_EINVAL, "ol_generate_rays: bad dtype %d", (int)dt);
+  return by_dtype(dt, [&](auto zero) {
+    return do_generate_rays<decltype(zero)>(p, n, in, out, status, st);
+  });
 }
 
 int ol_trace_spot(const ol_system* sys, ol_dtype dt, int64_t n_rays, const ol_raygen_params* p,
                   const ol_raygen_inputs* in, double cx, double cy, int32_t wavelength_index,
                   void* const hits[3], double* out7, uint32_t* status, void* stream) {
-  if (!sys) return failf(OL_EINVAL, "ol_trace_spot: system is NULL");
-  OL_CHECK_CONSISTENT(sys, "ol_trace_spot");
-  if (int rc = refuse_reference_newton("ol_trace_spot", sys)) return rc;
-  if (dt != OL_F32 && dt != OL_F64) return failf(OL_EINVAL, "ol_trace_spot: bad dtype %d", (int)dt);
+  SystemView v;
+  if (int rc = rule_system("ol_trace_spot", sys, v)) return rc;
+  if (int rc = rule_no_reference_newton("ol_trace_spot", v)) return rc;
+  if (int rc = rule_dtype("ol_trace_spot", dt)) return rc;
   if (!p || !in || !out7) return failf(OL_EINVAL, "ol_trace_spot: NULL argument");
   if (hits && (!hits[0] || !hits[1] || !hits[2]))
     return failf(OL_EINVAL, "ol_trace_spot: hits needs three planes");
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_spot: negative ray count");
-  if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return failf(OL_EINVAL, "ol_trace_spot: wavelength index %d outside [0, %d)", wavelength_index,
-                 sys->n_wl);
+  if (int rc = rule_count("ol_trace_spot", n_rays, "negative ray count")) return rc;
+  if (int rc = rule_wavelength("ol_trace_spot", v.n_wl, wavelength_index)) return rc;
   if (!(in->flags & OL_SPOT_POLARIZED_OK))
-    for (int32_t s = 0; s < sys->n_surf; ++s)
-      if (sys->coating[s] >= OL_COAT_FRESNEL)
-        return failf(OL_EINVAL,
-                     "Polarization must be set when surfaces have polarization-dependent "
-                     "coatings.");
-  if (n_rays > 0) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return failf(OL_EINVAL, "ol_trace_spot: current HIP device %d is not the system's device %d",
-                   cur, sys->device);
-  }
+    if (int rc = rule_polarisation_required(v, 0, v.n_surf - 1)) return rc;
+  if (n_rays > 0)
+    if (int rc = rule_current_device("ol_trace_spot", v)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dt == OL_F32)
-    return do_trace_spot<float>(sys, sys->f32, n_rays, p, in, cx, cy, wavelength_index, hits,
-                                out7, status, st);
-  return do_trace_spot<double>(sys, sys->f64, n_rays, p, in, cx, cy, wavelength_index, hits,
-                               out7, status, st);
+  return by_dtype(dt, sys, [&](auto zero, const auto& table) {
+    return do_trace_spot<decltype(zero)>(sys, table, n_rays, p, in, cx, cy, wavelength_index, hits,
+                                         out7, status, st);
+  });
 }
 
 int ol_trace_spot_batch(const ol_system* sys, ol_dtype dt, int64_t n_rays, const ol_raygen_params* p,
                         const ol_raygen_inputs* in, int32_t n_cells, const ol_spot_cell* cells,
                         void* hits, int64_t hits_stride, double* out8, uint32_t* status,
                         void* stream) {
-  if (!sys) return failf(OL_EINVAL, "ol_trace_spot_batch: system is NULL");
-  OL_CHECK_CONSISTENT(sys, "ol_trace_spot_batch");
-  if (int rc = refuse_reference_newton("ol_trace_spot_batch", sys)) return rc;
-  if (dt != OL_F32 && dt != OL_F64)
-    return failf(OL_EINVAL, "ol_trace_spot_batch: bad dtype %d", (int)dt);
+  SystemView v;
+  if (int rc = rule_system("ol_trace_spot_batch", sys, v)) return rc;
+  if (int rc = rule_no_reference_newton("ol_trace_spot_batch", v)) return rc;
+  if (int rc = rule_dtype("ol_trace_spot_batch", dt)) return rc;
   if (!p || !in || !out8 || (n_cells > 0 && !cells))
     return failf(OL_EINVAL, "ol_trace_spot_batch: NULL argument");
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_spot_batch: negative ray count");
+  if (int rc = rule_count("ol_trace_spot_batch", n_rays, "negative ray count")) return rc;
   if (n_cells < 0 || n_cells > OL_SPOT_BATCH_MAX_CELLS)
     return failf(OL_EINVAL, "ol_trace_spot_batch: %d cells outside [0, %d]", n_cells,
                  OL_SPOT_BATCH_MAX_CELLS);
@@ -1414,15 +1330,15 @@ int ol_trace_spot_batch(const ol_system* sys, ol_dtype dt, int64_t n_rays, const
   for (int32_t c = 0; c < n_cells; ++c) {
     const ol_system* from = cells[c].optics_of ? cells[c].optics_of : sys;
     if (from != sys) {
-      OL_CHECK_CONSISTENT(from, "ol_trace_spot_batch (optics_of)");
+      if (int rc = rule_consistent("ol_trace_spot_batch (optics_of)", from->consistent)) return rc;
       if (from->n_surf != sys->n_surf || from->device != sys->device)
         return failf(OL_EINVAL, "ol_trace_spot_batch: cell %d: optics_of has %d surfaces on device "
                                 "%d, the system %d on device %d", c, from->n_surf, from->device,
                      sys->n_surf, sys->device);
     }
-    if (cells[c].wavelength_index < 0 || cells[c].wavelength_index >= from->n_wl)
-      return failf(OL_EINVAL, "ol_trace_spot_batch: cell %d: wavelength index %d outside [0, %d)",
-                   c, cells[c].wavelength_index, from->n_wl);
+    char who[48];
+    snprintf(who, sizeof(who), "ol_trace_spot_batch: cell %d", c);
+    if (int rc = rule_wavelength(who, from->n_wl, cells[c].wavelength_index)) return rc;
     if (in->flags & OL_RAYGEN_CHECK_FIELD) {
       auto bad = [](double v) { return !(v >= -1.0 && v <= 1.0); };
       if (bad(cells[c].hx) || bad(cells[c].hy))  // real_ray_tracer.py:156-173, same text
@@ -1430,24 +1346,14 @@ int ol_trace_spot_batch(const ol_system* sys, ol_dtype dt, int64_t n_rays, const
     }
   }
   if (!(in->flags & OL_SPOT_POLARIZED_OK))
-    for (int32_t s = 0; s < sys->n_surf; ++s)
-      if (sys->coating[s] >= OL_COAT_FRESNEL)
-        return failf(OL_EINVAL,
-                     "Polarization must be set when surfaces have polarization-dependent "
-                     "coatings.");
-  if (n_rays > 0 && n_cells > 0) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return failf(OL_EINVAL,
-                   "ol_trace_spot_batch: current HIP device %d is not the system's device %d", cur,
-                   sys->device);
-  }
+    if (int rc = rule_polarisation_required(v, 0, v.n_surf - 1)) return rc;
+  if (n_rays > 0 && n_cells > 0)
+    if (int rc = rule_current_device("ol_trace_spot_batch", v)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dt == OL_F32)
-    return do_trace_spot_batch<float>(sys, sys->f32, n_rays, p, in, n_cells, cells, hits,
-                                      hits_stride, out8, status, st);
-  return do_trace_spot_batch<double>(sys, sys->f64, n_rays, p, in, n_cells, cells, hits,
-                                     hits_stride, out8, status, st);
+  return by_dtype(dt, sys, [&](auto zero, const auto& table) {
+    return do_trace_spot_batch<decltype(zero)>(sys, table, n_rays, p, in, n_cells, cells, hits,
+                                               hits_stride, out8, status, st);
+  });
 }
 
 int ol_irradiance(ol_dtype dt, int64_t n_rays, const void* x, const void* y, const void* power,
@@ -1455,20 +1361,17 @@ int ol_irradiance(ol_dtype dt, int64_t n_rays, const void* x, const void* y, con
                   double* hist, void* stream) {
   if (!x || !y || !power || !x_edges || !y_edges || !hist)
     return failf(OL_EINVAL, "ol_irradiance: NULL argument");
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_irradiance: negative count");
+  if (int rc = rule_count("ol_irradiance", n_rays, "negative count")) return rc;
   if (nx < 1 || ny < 1 || (int64_t)nx * ny > (int64_t)1 << 28)
     return failf(OL_EINVAL, "ol_irradiance: %d x %d bins", nx, ny);
   if (n_rays == 0) return OL_OK;
+  if (int rc = rule_dtype("ol_irradiance", dt)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (dt == OL_F32)
-    e = ol::launch_irradiance<float>(n_rays, (const float*)x, (const float*)y,
-                                     (const float*)power, x_edges, nx, y_edges, ny, hist, st);
-  else if (dt == OL_F64)
-    e = ol::launch_irradiance<double>(n_rays, (const double*)x, (const double*)y,
-                                      (const double*)power, x_edges, nx, y_edges, ny, hist, st);
-  else
-    return failf(OL_EINVAL, "ol_irradiance: bad dtype %d", (int)dt);
+  const hipError_t e = by_dtype(dt, [&](auto zero) {
+    using T = decltype(zero);
+    return ol::launch_irradiance<T>(n_rays, (const T*)x, (const T*)y, (const T*)power, x_edges, nx,
+                                    y_edges, ny, hist, st);
+  });
   if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
@@ -1478,21 +1381,17 @@ int ol_radial_energy(ol_dtype dt, int64_t n_rays, const void* x, const void* y,
                      int32_t n_steps, double* bins, void* stream) {
   if (!x || !y || !intensity || !r_step || !bins)
     return failf(OL_EINVAL, "ol_radial_energy: NULL argument");
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_radial_energy: negative count");
+  if (int rc = rule_count("ol_radial_energy", n_rays, "negative count")) return rc;
   if (n_steps < 1 || n_steps > 1024)
     return failf(OL_EINVAL, "ol_radial_energy: n_steps %d outside [1, 1024]", n_steps);
   if (n_rays == 0) return OL_OK;
+  if (int rc = rule_dtype("ol_radial_energy", dt)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (dt == OL_F32)
-    e = ol::launch_radial_energy<float>(n_rays, (const float*)x, (const float*)y,
-                                        (const float*)intensity, cx, cy, r_step, n_steps, bins, st);
-  else if (dt == OL_F64)
-    e = ol::launch_radial_energy<double>(n_rays, (const double*)x, (const double*)y,
-                                         (const double*)intensity, cx, cy, r_step, n_steps, bins,
-                                         st);
-  else
-    return failf(OL_EINVAL, "ol_radial_energy: bad dtype %d", (int)dt);
+  const hipError_t e = by_dtype(dt, [&](auto zero) {
+    using T = decltype(zero);
+    return ol::launch_radial_energy<T>(n_rays, (const T*)x, (const T*)y, (const T*)intensity, cx,
+                                       cy, r_step, n_steps, bins, st);
+  });
   if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
@@ -1503,24 +1402,17 @@ int ol_polarized_intensity(ol_dtype dt, int64_t n_rays, const void* prt, int32_t
                            uint32_t* status, void* stream) {
   if (!prt || !k0 || !k0[0] || !k0[1] || !k0[2] || !i0 || !state || !intensity)
     return failf(OL_EINVAL, "ol_polarized_intensity: NULL argument");
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_polarized_intensity: negative count");
+  if (int rc = rule_count("ol_polarized_intensity", n_rays, "negative count")) return rc;
   if (n_rays == 0) return OL_OK;
   ol::PolStateDev s{state->is_polarized, state->Ex, state->Ey, state->phase_x, state->phase_y};
+  if (int rc = rule_dtype("ol_polarized_intensity", dt)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (dt == OL_F32) {
-    const float* k[3] = {(const float*)k0[0], (const float*)k0[1], (const float*)k0[2]};
-    e = ol::launch_pol_intensity<float>(n_rays, (const float*)prt, prt_complex != 0, k,
-                                        (const float*)i0, s,
-                                        (float*)intensity, status, st);
-  } else if (dt == OL_F64) {
-    const double* k[3] = {(const double*)k0[0], (const double*)k0[1], (const double*)k0[2]};
-    e = ol::launch_pol_intensity<double>(n_rays, (const double*)prt, prt_complex != 0, k,
-                                         (const double*)i0, s,
-                                         (double*)intensity, status, st);
-  } else {
-    return failf(OL_EINVAL, "ol_polarized_intensity: bad dtype %d", (int)dt);
-  }
+  const hipError_t e = by_dtype(dt, [&](auto zero) {
+    using T = decltype(zero);
+    const T* k[3] = {(const T*)k0[0], (const T*)k0[1], (const T*)k0[2]};
+    return ol::launch_pol_intensity<T>(n_rays, (const T*)prt, prt_complex != 0, k, (const T*)i0, s,
+                                       (T*)intensity, status, st);
+  });
   if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
@@ -1530,33 +1422,24 @@ int ol_wavefront_opd(const ol_wavefront_params* p, ol_dtype dt, int64_t n_rays,
                      void* opd_waves, void* const pupil[3], void* stream) {
   if (!p || !rays || !px || !py || !opd_waves)
     return failf(OL_EINVAL, "ol_wavefront_opd: NULL argument");
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_wavefront_opd: negative count");
+  if (int rc = rule_count("ol_wavefront_opd", n_rays, "negative count")) return rc;
   if (n_rays == 0) return OL_OK;
-  for (int k = 0; k < 7; ++k)
-    if (!rays[k]) return failf(OL_EINVAL, "ol_wavefront_opd: rays[%d] is NULL", k);
+  if (int rc = rule_planes("ol_wavefront_opd", "rays", rays, 7)) return rc;
   if (pupil && (!pupil[0] || !pupil[1] || !pupil[2]))
     return failf(OL_EINVAL, "ol_wavefront_opd: pupil planes must all be given or pupil = NULL");
   ol::WavefrontDev d{p->xc, p->yc, p->zc, p->R, p->n_image, p->opd_ref,
                      p->ux, p->uy, p->half_epd, p->wavelength_um, p->nx, p->ny, p->nz};
+  if (int rc = rule_dtype("ol_wavefront_opd", dt)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (dt == OL_F32) {
-    const float* r[7];
-    for (int k = 0; k < 7; ++k) r[k] = static_cast<const float*>(rays[k]);
-    float* pu[3] = {pupil ? (float*)pupil[0] : nullptr, pupil ? (float*)pupil[1] : nullptr,
-                    pupil ? (float*)pupil[2] : nullptr};
-    e = ol::launch_wavefront<float>(d, n_rays, r, (const float*)px, (const float*)py,
-                                    (float*)opd_waves, pupil ? pu : nullptr, st);
-  } else if (dt == OL_F64) {
-    const double* r[7];
-    for (int k = 0; k < 7; ++k) r[k] = static_cast<const double*>(rays[k]);
-    double* pu[3] = {pupil ? (double*)pupil[0] : nullptr, pupil ? (double*)pupil[1] : nullptr,
-                     pupil ? (double*)pupil[2] : nullptr};
-    e = ol::launch_wavefront<double>(d, n_rays, r, (const double*)px, (const double*)py,
-                                     (double*)opd_waves, pupil ? pu : nullptr, st);
-  } else {
-    return failf(OL_EINVAL, "ol_wavefront_opd: bad dtype %d", (int)dt);
-  }
+  const hipError_t e = by_dtype(dt, [&](auto zero) {
+    using T = decltype(zero);
+    const T* r[7];
+    for (int k = 0; k < 7; ++k) r[k] = static_cast<const T*>(rays[k]);
+    T* pu[3] = {pupil ? (T*)pupil[0] : nullptr, pupil ? (T*)pupil[1] : nullptr,
+                pupil ? (T*)pupil[2] : nullptr};
+    return ol::launch_wavefront<T>(d, n_rays, r, (const T*)px, (const T*)py, (T*)opd_waves,
+                                   pupil ? pu : nullptr, st);
+  });
   if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
@@ -1565,9 +1448,9 @@ int ol_trace_opd(const ol_system* sys, ol_dtype dt, int64_t n_rays, const ol_ray
                  const ol_raygen_inputs* in, const ol_wavefront_params* w,
                  int32_t wavelength_index, void* opd_waves, void* intensity,
                  void* const pupil[3], double* moments12, uint32_t* status, void* stream) {
-  if (!sys) return failf(OL_EINVAL, "ol_trace_opd: system is NULL");
-  OL_CHECK_CONSISTENT(sys, "ol_trace_opd");
-  if (int rc = refuse_reference_newton("ol_trace_opd", sys)) return rc;
+  SystemView v;
+  if (int rc = rule_system("ol_trace_opd", sys, v)) return rc;
+  if (int rc = rule_no_reference_newton("ol_trace_opd", v)) return rc;
   if (dt != OL_F64)
     return failf(dt == OL_F32 ? OL_EUNSUPPORTED : OL_EINVAL,
                  "ol_trace_opd: wavefront work is fp64 only (dtype %d)", (int)dt);
@@ -1575,50 +1458,26 @@ int ol_trace_opd(const ol_system* sys, ol_dtype dt, int64_t n_rays, const ol_ray
     return failf(OL_EINVAL, "ol_trace_opd: NULL argument");
   if (pupil && (!pupil[0] || !pupil[1] || !pupil[2]))
     return failf(OL_EINVAL, "ol_trace_opd: pupil planes must all be given or pupil = NULL");
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_opd: negative ray count");
-  if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return failf(OL_EINVAL, "ol_trace_opd: wavelength index %d outside [0, %d)", wavelength_index,
-                 sys->n_wl);
-  for (int32_t s = 0; s < sys->n_surf; ++s)
-    if (sys->coating[s] >= OL_COAT_FRESNEL)
-      return failf(OL_EINVAL,
-                   "Polarization must be set when surfaces have polarization-dependent "
-                   "coatings.");
-  if (n_rays > 0) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-      return failf(OL_EINVAL, "ol_trace_opd: current HIP device %d is not the system's device %d",
-                   cur, sys->device);
-  }
+  if (int rc = rule_count("ol_trace_opd", n_rays, "negative ray count")) return rc;
+  if (int rc = rule_wavelength("ol_trace_opd", v.n_wl, wavelength_index)) return rc;
+  if (int rc = rule_polarisation_required(v, 0, v.n_surf - 1)) return rc;
+  if (n_rays > 0)
+    if (int rc = rule_current_device("ol_trace_opd", v)) return rc;
   return do_trace_opd<double>(sys, sys->f64, n_rays, p, in, w, wavelength_index, opd_waves,
                               intensity, pupil, moments12, status,
                               static_cast<hipStream_t>(stream));
 }
 
+// what ol_wavefront_reference and ol_trace_opd_dev check first, in this order
 static int opd_common_checks(const char* who, const ol_system* sys, ol_dtype dt,
                              int32_t wavelength_index) {
-  if (!sys) return failf(OL_EINVAL, "%s: system is NULL", who);
-  if (!sys->consistent)
-    return failf(OL_EINVAL, "%s: the system's tables are inconsistent after a failed "
-                            "ol_system_update (destroy it and create a new one)", who);
-  if (dt == OL_F32)
-    return failf(OL_EUNSUPPORTED, "%s: wavefront work is fp64 only (an OPD in waves needs 1e-9 "
-                                  "of the path length)", who);
-  if (dt != OL_F64) return failf(OL_EINVAL, "%s: bad dtype %d", who, (int)dt);
-  if (wavelength_index < 0 || wavelength_index >= sys->n_wl)
-    return failf(OL_EINVAL, "%s: wavelength index %d outside [0, %d)", who, wavelength_index,
-                 sys->n_wl);
-  if (int rc = refuse_reference_newton(who, sys)) return rc;
-  for (int32_t s = 0; s < sys->n_surf; ++s)
-    if (sys->coating[s] >= OL_COAT_FRESNEL)
-      return failf(OL_EINVAL,
-                   "Polarization must be set when surfaces have polarization-dependent "
-                   "coatings.");
-  int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess || cur != sys->device)
-    return failf(OL_EINVAL, "%s: current HIP device %d is not the system's device %d", who, cur,
-                 sys->device);
-  return OL_OK;
+  SystemView v;
+  if (int rc = rule_system(who, sys, v)) return rc;
+  if (int rc = rule_fp64_only(who, dt)) return rc;
+  if (int rc = rule_wavelength(who, v.n_wl, wavelength_index)) return rc;
+  if (int rc = rule_no_reference_newton(who, v)) return rc;
+  if (int rc = rule_polarisation_required(v, 0, v.n_surf - 1)) return rc;
+  return rule_current_device(who, v);
 }
 
 int ol_wavefront_reference(const ol_system* sys, ol_dtype dt, const ol_raygen_params* p,
@@ -1646,7 +1505,7 @@ int ol_trace_opd_dev(const ol_system* sys, ol_dtype dt, int64_t n_rays,
     return failf(OL_EINVAL, "ol_trace_opd_dev: NULL argument");
   if (pupil && (!pupil[0] || !pupil[1] || !pupil[2]))
     return failf(OL_EINVAL, "ol_trace_opd_dev: pupil needs three planes");
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_opd_dev: negative ray count");
+  if (int rc = rule_count("ol_trace_opd_dev", n_rays, "negative ray count")) return rc;
   return do_trace_opd<double>(sys, sys->f64, n_rays, p, in, nullptr, wavelength_index, opd_waves,
                               intensity, pupil, moments12, status,
                               static_cast<hipStream_t>(stream), reference_dev);
@@ -1668,14 +1527,13 @@ int ol_wavefront_fit(int32_t kind, const ol_wavefront_params* w, double trim_std
     return failf(OL_EINVAL, "ol_wavefront_fit: NULL argument");
   if (kind != OL_FIT_CENTROID && kind != OL_FIT_BEST_FIT)
     return failf(OL_EINVAL, "ol_wavefront_fit: unknown kind %d", (int)kind);
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_wavefront_fit: negative count");
+  if (int rc = rule_count("ol_wavefront_fit", n_rays, "negative count")) return rc;
   if (flags & ~(uint32_t)(OL_FIT_STD_DDOF1 | OL_FIT_PISTON_SKIPS_NAN))
     return failf(OL_EINVAL, "ol_wavefront_fit: unknown flags 0x%x", (unsigned)flags);
   if (!(w->n_image > 0.0) || !(w->wavelength_um > 0.0))
     return failf(OL_EINVAL, "ol_wavefront_fit: n_image %g, wavelength %g", w->n_image,
                  w->wavelength_um);
-  for (int k = 0; k < 8; ++k)
-    if (!rays[k]) return failf(OL_EINVAL, "ol_wavefront_fit: rays[%d] is NULL", k);
+  if (int rc = rule_planes("ol_wavefront_fit", "rays", rays, 8)) return rc;
   ol::FitArgs a{};
   a.p.ni = w->n_image;
   a.p.inv_w = 1.0 / (w->wavelength_um * 1e-3);
@@ -1705,9 +1563,8 @@ int ol_wavefront_opd_fitted(int64_t n_rays, const double* const rays[7], const d
                             double* const pupil[3], void* stream) {
   if (!rays || !px || !py || !reference_dev || !opd_waves)
     return failf(OL_EINVAL, "ol_wavefront_opd_fitted: NULL argument");
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_wavefront_opd_fitted: negative count");
-  for (int k = 0; k < 7; ++k)
-    if (!rays[k]) return failf(OL_EINVAL, "ol_wavefront_opd_fitted: rays[%d] is NULL", k);
+  if (int rc = rule_count("ol_wavefront_opd_fitted", n_rays, "negative count")) return rc;
+  if (int rc = rule_planes("ol_wavefront_opd_fitted", "rays", rays, 7)) return rc;
   if (pupil && (!pupil[0] || !pupil[1] || !pupil[2]))
     return failf(OL_EINVAL, "ol_wavefront_opd_fitted: pupil needs three planes");
   if (n_rays == 0) return OL_OK;
@@ -1735,18 +1592,14 @@ int ol_pupil_fill(ol_dtype dt, int64_t n_rays, const void* opd_waves, const void
   const double zero[3] = {0.0, 0.0, 0.0};
   const double* co = plane ? plane : zero;
   const int32_t pad = (grid_size - n_side) / 2;  // psf/fft.py:139-160
+  if (int rc = rule_dtype("ol_pupil_fill", dt)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (dt == OL_F32)
-    e = ol::launch_pupil_fill<float>(n_rays, (const float*)opd_waves, (const float*)intensity,
-                                     (const float*)pupil_x, (const float*)pupil_y, co, cell,
-                                     n_side, grid_size, pad, grid, st);
-  else if (dt == OL_F64)
-    e = ol::launch_pupil_fill<double>(n_rays, (const double*)opd_waves, (const double*)intensity,
-                                      (const double*)pupil_x, (const double*)pupil_y, co, cell,
-                                      n_side, grid_size, pad, grid, st);
-  else
-    return failf(OL_EINVAL, "ol_pupil_fill: bad dtype %d", (int)dt);
+  const hipError_t e = by_dtype(dt, [&](auto zero) {
+    using T = decltype(zero);
+    return ol::launch_pupil_fill<T>(n_rays, (const T*)opd_waves, (const T*)intensity,
+                                    (const T*)pupil_x, (const T*)pupil_y, co, cell, n_side,
+                                    grid_size, pad, grid, st);
+  });
   if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
@@ -1768,16 +1621,13 @@ int ol_pupil_points(int32_t kind, int32_t param, ol_dtype dt, int64_t n_points,
     if (n_points > 0 && (!row_first || !row_offset))
       return failf(OL_EINVAL, "ol_pupil_points: the uniform sampler needs its row tables");
   }
+  if (int rc = rule_dtype("ol_pupil_points", dt)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (dt == OL_F32)
-    e = ol::launch_pupil_points<float>(kind, param, n_points, row_first, row_offset,
-                                       static_cast<float*>(x), static_cast<float*>(y), st);
-  else if (dt == OL_F64)
-    e = ol::launch_pupil_points<double>(kind, param, n_points, row_first, row_offset,
-                                        static_cast<double*>(x), static_cast<double*>(y), st);
-  else
-    return failf(OL_EINVAL, "ol_pupil_points: bad dtype %d", (int)dt);
+  const hipError_t e = by_dtype(dt, [&](auto zero) {
+    using T = decltype(zero);
+    return ol::launch_pupil_points<T>(kind, param, n_points, row_first, row_offset,
+                                      static_cast<T*>(x), static_cast<T*>(y), st);
+  });
   if (e != hipSuccess) return failf(OL_EHIP, "pupil launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
@@ -1787,17 +1637,13 @@ int ol_math_probe(int32_t op, ol_dtype dt, int64_t n, const void* a, const void*
   if (op < 0 || op > 3) return failf(OL_EINVAL, "ol_math_probe: op must be 0..3");
   if (n < 0 || (n > 0 && (!a || !out || (op == 1 && !b))))
     return failf(OL_EINVAL, "ol_math_probe: NULL argument");
+  if (int rc = rule_dtype("ol_math_probe", dt)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (dt == OL_F32)
-    e = ol::launch_math_probe<float>(op, n, static_cast<const float*>(a),
-                                     static_cast<const float*>(b), static_cast<float*>(out), st);
-  else if (dt == OL_F64)
-    e = ol::launch_math_probe<double>(op, n, static_cast<const double*>(a),
-                                      static_cast<const double*>(b), static_cast<double*>(out),
-                                      st);
-  else
-    return failf(OL_EINVAL, "ol_math_probe: bad dtype %d", (int)dt);
+  const hipError_t e = by_dtype(dt, [&](auto zero) {
+    using T = decltype(zero);
+    return ol::launch_math_probe<T>(op, n, static_cast<const T*>(a), static_cast<const T*>(b),
+                                    static_cast<T*>(out), st);
+  });
   if (e != hipSuccess) return failf(OL_EHIP, "probe launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
@@ -1843,13 +1689,14 @@ int ol_arena_free(void* arena) {
 int ol_spot_moments(ol_dtype dt, int64_t n_rays, const void* x, const void* y,
                     const void* intensity, double* out6, void* stream) {
   if (!x || !y || !intensity || !out6) return failf(OL_EINVAL, "ol_spot_moments: NULL argument");
-  if (n_rays <= 0) return n_rays == 0 ? OL_OK : failf(OL_EINVAL, "ol_spot_moments: negative count");
+  if (int rc = rule_count("ol_spot_moments", n_rays, "negative count")) return rc;
+  if (n_rays == 0) return OL_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e = dt == OL_F32
-                     ? ol::launch_spot_moments<float>(n_rays, (const float*)x, (const float*)y,
-                                                      (const float*)intensity, out6, st)
-                     : ol::launch_spot_moments<double>(n_rays, (const double*)x, (const double*)y,
-                                                       (const double*)intensity, out6, st);
+  const hipError_t e = by_dtype(dt, [&](auto zero) {
+    using T = decltype(zero);
+    return ol::launch_spot_moments<T>(n_rays, (const T*)x, (const T*)y, (const T*)intensity, out6,
+                                      st);
+  });
   if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }
@@ -1857,13 +1704,14 @@ int ol_spot_moments(ol_dtype dt, int64_t n_rays, const void* x, const void* y,
 int ol_spot_max_r2(ol_dtype dt, int64_t n_rays, const void* x, const void* y,
                    const void* intensity, double cx, double cy, double* out1, void* stream) {
   if (!x || !y || !intensity || !out1) return failf(OL_EINVAL, "ol_spot_max_r2: NULL argument");
-  if (n_rays <= 0) return n_rays == 0 ? OL_OK : failf(OL_EINVAL, "ol_spot_max_r2: negative count");
+  if (int rc = rule_count("ol_spot_max_r2", n_rays, "negative count")) return rc;
+  if (n_rays == 0) return OL_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e = dt == OL_F32
-                     ? ol::launch_spot_max_r2<float>(n_rays, (const float*)x, (const float*)y,
-                                                     (const float*)intensity, cx, cy, out1, st)
-                     : ol::launch_spot_max_r2<double>(n_rays, (const double*)x, (const double*)y,
-                                                      (const double*)intensity, cx, cy, out1, st);
+  const hipError_t e = by_dtype(dt, [&](auto zero) {
+    using T = decltype(zero);
+    return ol::launch_spot_max_r2<T>(n_rays, (const T*)x, (const T*)y, (const T*)intensity, cx, cy,
+                                     out1, st);
+  });
   if (e != hipSuccess) return failf(OL_EHIP, "launch failed: %s", hipGetErrorString(e));
   return OL_OK;
 }

@@ -10,7 +10,7 @@
 // (surface_math.h: interact<>, as the fused kernels use it), the way back to the global frame and
 // the stores of the ray state and of the recorded row.  Nothing is shared between lanes but the
 // OR of the status word.  The fused kernels do not know these surfaces: their entry points refuse
-// a range that holds one (capi.hip: refuse_forbes).
+// a range that holds one (entry_rules.h: rule_no_forbes).
 //
 // Shape of the launch.  8 planes read, up to 16 written, per ray some hundred fp operations per
 // Newton iteration: at millions of rays the launch is bound by memory, at the thousands of rays of
@@ -25,8 +25,7 @@
 
 #include "../../include/optiland_hip.h"
 #include "forbes_device.h"
-#include "last_error.h"
-#include "system_view.h"
+#include "forbes_host.h"
 #include "trace_launch.h"
 
 // (namespace ol, not an anonymous one: tools/asm_stats.py and rocprofv3 name the kernels)
@@ -103,47 +102,12 @@ extern "C" int ol_trace_forbes(const ol_system* sys, ol_dtype dt, int64_t n_rays
                                void* const rays[8], int32_t wavelength_index, void* record_row,
                                int64_t record_stride, int32_t surface, uint32_t flags,
                                uint32_t* status, void* stream) {
-  if (!sys) return failf(OL_EINVAL, "ol_trace_forbes: system is NULL");
-  const SystemView v = system_view(sys);
-  if (!v.consistent)
-    return failf(OL_EINVAL, "ol_trace_forbes: the system's tables are inconsistent after a failed "
-                            "ol_system_update (destroy it and create a new one)");
-  if (dt != OL_F32 && dt != OL_F64)
-    return failf(OL_EINVAL, "ol_trace_forbes: bad dtype %d", (int)dt);
-  if (n_rays < 0) return failf(OL_EINVAL, "ol_trace_forbes: negative ray count");
-  if (surface < 0 || surface >= v.n_surf)
-    return failf(OL_EINVAL, "ol_trace_forbes: surface %d outside [0, %d)", surface, v.n_surf);
-  if (!is_forbes_kind(v.geom[surface]))
-    return failf(OL_EINVAL, "ol_trace_forbes: surface %d is not a Forbes surface (geometry kind "
-                            "%d): trace it with ol_trace", surface, v.geom[surface]);
-  if (wavelength_index < 0 || wavelength_index >= v.n_wl)
-    return failf(OL_EINVAL, "ol_trace_forbes: wavelength index %d outside [0, %d)",
-                 wavelength_index, v.n_wl);
-  if (flags & ~(uint32_t)(OL_TRACE_WRITE_RAYS | OL_TRACE_MIDRANGE))
-    return failf(OL_EINVAL, "ol_trace_forbes: flags 0x%x: OL_TRACE_WRITE_RAYS and "
-                            "OL_TRACE_MIDRANGE only", flags);
-  if (v.coating[surface] >= OL_COAT_FRESNEL)
-    return failf(OL_EUNSUPPORTED, "ol_trace_forbes: surface %d carries a polarisation-dependent "
-                                  "coating (unpolarised launches only)", surface);
+  if (int rc = forbes_check(sys, dt, n_rays, rays, wavelength_index, record_row, record_stride,
+                            surface, flags))
+    return rc;
   if (n_rays == 0) return OL_OK;
-  if (n_rays > (int64_t)0x7fffffff * 64)
-    return failf(OL_EINVAL, "ol_trace_forbes: %lld rays are more than one launch takes",
-                 (long long)n_rays);
-  if (!rays) return failf(OL_EINVAL, "ol_trace_forbes: rays is NULL");
-  for (int k = 0; k < 8; ++k)
-    if (!rays[k]) return failf(OL_EINVAL, "ol_trace_forbes: rays[%d] is NULL", k);
-  if (record_row && record_stride < n_rays)
-    return failf(OL_EINVAL, "ol_trace_forbes: record_stride %lld < n_rays %lld",
-                 (long long)record_stride, (long long)n_rays);
-  if (!record_row && !(flags & OL_TRACE_WRITE_RAYS))
-    return failf(OL_EINVAL, "ol_trace_forbes: nothing to write (no record_row, no "
-                            "OL_TRACE_WRITE_RAYS)");
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != v.device)
-      return failf(OL_EINVAL, "ol_trace_forbes: current HIP device %d is not the system's device "
-                              "%d", cur, v.device);
-  }
+  const SystemView v = system_view(sys);
+  if (int rc = rule_current_device("ol_trace_forbes", v)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (dt == OL_F32)
     forbes_launch<float>(v.surf32, v.cold32, v.optics32, v.coeffs32, surface, v.n_wl,

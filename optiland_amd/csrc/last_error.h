@@ -1,7 +1,8 @@
 // last_error.h -- what the host side of every translation unit shares: the library's one
 // thread-local error message (ol_last_error) and the stream-ordered workspace of an entry point.
 // failf is defined in capi.hip; capi.hip itself references no symbol of the other units
-// (tests/hostmath links it alone).
+// (tests/hostmath links it alone).  The argument rules the entry points share, and their texts,
+// are stated once in entry_rules.h, which builds on this header and on system_view.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

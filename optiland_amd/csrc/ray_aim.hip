@@ -102,12 +102,7 @@ extern "C" int ol_aim_rays(const ol_system* sys, int64_t n_rays, int32_t wavelen
     return failf(OL_EINVAL, "ol_aim_rays: %lld rays are more than one launch takes",
                  (long long)n_rays);
   const SystemView v = system_view(sys);
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != v.device)
-      return failf(OL_EINVAL, "ol_aim_rays: current HIP device %d is not the system's device %d",
-                   cur, v.device);
-  }
+  if (int rc = rule_current_device("ol_aim_rays", v)) return rc;
   AimArgs a{};
   a.table = AimTable{v.surf, v.cold, v.optics, v.coeffs, first_surface, stop_surface, v.n_wl,
                      wavelength_index};

@@ -1,7 +1,8 @@
 // system_view.h -- what a translation unit other than capi.hip may know of an `ol_system`: the
 // fp64 device table and the host-side facts the entry points validate against.  `ol_system`
 // itself stays private to capi.hip, which defines the two functions below; capi.hip references
-// no symbol of the units that use them (tests/hostmath links it alone).
+// no symbol of the units that use them (tests/hostmath links it alone).  The rules every entry
+// point checks a system and its arguments against are functions of this view: entry_rules.h.
 #pragma once
 #include <stdint.h>
 

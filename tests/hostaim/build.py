@@ -1,27 +1,20 @@
-"""Build tests/hostaim/_build/hostaim (and hostaim_asan): the ray-aiming solve of
-optiland_amd/csrc/ray_aim_device.h compiled for the HOST as a stand-alone program -- a checker
-for boxes without a GPU.  See main.hip for what it is and is not.
+"""Build tests/hostaim/_build/hostaim (and hostaim_asan): the ray-aiming solve of optiland_amd/csrc/
+ray_aim_device.h compiled for the HOST as a stand-alone program -- a checker for boxes without
+a GPU.  See main.hip for what it is and is not.
 
     python tests/hostaim/build.py [--sanitize]
 
-main.hip is compiled with the flags of tests/hostmath/build.py and linked with the two objects
-that build leaves behind (the host-only csrc/capi.hip and the stand-in HIP runtime of
-tests/hostmath/harness.hip).  `sanitize=True`: all three with AddressSanitizer +
-UndefinedBehaviorSanitizer, the runtime linked INTO the program -- it runs as an ordinary child
-process, nothing is preloaded.
+The recipe is `build_program` of tests/hostmath/build.py: main.hip with that build's flags, linked
+with the two objects it leaves behind (the host-only csrc/capi.hip and the stand-in HIP runtime of
+tests/hostmath/harness.hip), plain or with AddressSanitizer + UndefinedBehaviorSanitizer.
 """
 
 from __future__ import annotations
 
 import importlib.util
 import os
-import shutil
-import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-CSRC = os.path.join(ROOT, "optiland_amd", "csrc")
-OUT = os.path.join(HERE, "_build")
 
 
 def _hostmath():
@@ -37,40 +30,8 @@ def available() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False, sanitize: bool = False) -> str:
-    hm = _hostmath()
-    hm.build(force=force, verbose=verbose, sanitize=sanitize)   # capi.o / harness.o up to date
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    os.makedirs(OUT, exist_ok=True)
-    suffix = "_asan" if sanitize else ""
-    exe = os.path.join(OUT, "hostaim" + suffix)
-    objs = [os.path.join(hm.OUT, f"{name}{suffix}.o") for name in ("capi", "harness")]
-    src = os.path.join(HERE, "main.hip")
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + objs + [
-        src, os.path.join(ROOT, "include", "optiland_hip.h"), os.path.abspath(__file__)]
-    if not force and os.path.exists(exe) and \
-            all(os.path.getmtime(d) <= os.path.getmtime(exe) for d in deps):
-        return exe
-    flags = ["--offload-host-only", "-std=c++17", "-fPIC", "-ffp-contract=on", "-fno-math-errno",
-             "-Wall"] + (["-mfma"] if hm._cpu_has_fma() else [])
-    flags += ["-O1", "-g1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-              "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]
-    obj = os.path.join(OUT, f"main{suffix}.o")
-    cmd = [hipcc, *flags, "-c", src, "-o", obj]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd, stderr=None if verbose else subprocess.DEVNULL)
-    if sanitize:
-        clang = os.path.join(os.path.dirname(os.path.realpath(hipcc)), "..", "lib", "llvm", "bin",
-                             "clang++")
-        if not os.path.exists(clang):
-            clang = "/opt/rocm/lib/llvm/bin/clang++"
-        cmd = [clang, "-fsanitize=address,undefined", obj, *objs, "-o", exe]
-    else:
-        cmd = ["g++", obj, *objs, "-o", exe]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    return exe
+    return _hostmath().build_program("hostaim", os.path.join(HERE, "main.hip"), force=force,
+                                     verbose=verbose, sanitize=sanitize)
 
 
 if __name__ == "__main__":

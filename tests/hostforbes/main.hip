@@ -6,6 +6,8 @@
 //   hostforbes refuse <case file>   every range-walking entry point on the case's system: one
 //                                   line per call with its return code (no launch happens)
 //   hostforbes create <case file>   ol_system_create alone: its return code and message
+//   hostforbes rules <case file>    the argument rules of ol_trace_forbes (forbes_host.h) on the
+//                                   case's system: one line per call
 //
 // Linked with the host-only compile of csrc/capi.hip (ol_system_create builds the table the
 // kernel reads) and tests/hostmath/harness.hip (the stand-in for the few HIP runtime calls
@@ -27,6 +29,7 @@
 
 #include "../../include/optiland_hip.h"
 #include "../../optiland_amd/csrc/forbes_device.h"
+#include "../../optiland_amd/csrc/forbes_host.h"
 #include "../../optiland_amd/csrc/ray_aim_host.h"
 #include "../../optiland_amd/csrc/system_view.h"
 
@@ -188,15 +191,56 @@ int refuse(const Case& c, ol_system* sys) {
   return 0;
 }
 
+// ol_trace_forbes's own rules, one broken at a time (every plane is a real one of the case)
+int rules(Case& c, ol_system* sys) {
+  using namespace ol;
+  const int32_t wl = (int32_t)c.h[6], s = (int32_t)c.h[5], n_surf = (int32_t)c.h[1];
+  const int64_t n = c.h[4];
+  std::vector<double> row(8 * (size_t)n + 1);
+  void* rays[8];
+  for (int k = 0; k < 8; ++k) rays[k] = c.plane[k].data();
+  auto say = [](const char* what, int rc) {
+    printf("%s: %d %s\n", what, rc, rc ? ol_last_error() : "ok");
+  };
+  const uint32_t wr = OL_TRACE_WRITE_RAYS;
+  say("good", forbes_check(sys, OL_F64, n, rays, wl, row.data(), n, s, 0));
+  say("good fp32 midrange", forbes_check(sys, OL_F32, n, rays, wl, nullptr, 0, s,
+                                         wr | OL_TRACE_MIDRANGE));
+  say("empty", forbes_check(sys, OL_F64, 0, nullptr, wl, nullptr, 0, s, 0));
+  say("null system", forbes_check(nullptr, OL_F64, n, rays, wl, row.data(), n, s, 0));
+  say("dtype", forbes_check(sys, (ol_dtype)5, n, rays, wl, row.data(), n, s, 0));
+  say("negative count", forbes_check(sys, OL_F64, -1, rays, wl, row.data(), n, s, 0));
+  say("surface -1", forbes_check(sys, OL_F64, n, rays, wl, row.data(), n, -1, 0));
+  say("surface past the table", forbes_check(sys, OL_F64, n, rays, wl, row.data(), n, n_surf, 0));
+  say("not a forbes row", forbes_check(sys, OL_F64, n, rays, wl, row.data(), n, s + 1, 0));
+  say("wavelength", forbes_check(sys, OL_F64, n, rays, (int32_t)c.h[2], row.data(), n, s, 0));
+  say("wavelength -1", forbes_check(sys, OL_F64, n, rays, -1, row.data(), n, s, 0));
+  say("flags", forbes_check(sys, OL_F64, n, rays, wl, row.data(), n, s, OL_TRACE_PRT_COMPLEX));
+  say("too many", forbes_check(sys, OL_F64, ((int64_t)0x7fffffff * 64) + 1, rays, wl, nullptr, 0, s, wr));
+  say("null rays", forbes_check(sys, OL_F64, n, nullptr, wl, row.data(), n, s, 0));
+  { void* b[8];
+    for (int k = 0; k < 8; ++k) b[k] = k == 5 ? nullptr : rays[k];
+    say("null plane", forbes_check(sys, OL_F64, n, b, wl, row.data(), n, s, 0)); }
+  say("stride", forbes_check(sys, OL_F64, n, rays, wl, row.data(), n - 1, s, 0));
+  say("nothing to write", forbes_check(sys, OL_F64, n, rays, wl, nullptr, 0, s, 0));
+  // precedence: the first broken rule answers
+  say("all at once", forbes_check(sys, (ol_dtype)5, -1, nullptr, -1, nullptr, 0, n_surf, ~0u));
+  say("all but dtype", forbes_check(sys, OL_F64, -1, nullptr, -1, nullptr, 0, n_surf, ~0u));
+  say("surface before wavelength", forbes_check(sys, OL_F64, n, nullptr, -1, nullptr, 0, n_surf, ~0u));
+  say("wavelength before flags", forbes_check(sys, OL_F64, n, nullptr, -1, nullptr, 0, s, ~0u));
+  say("flags before planes", forbes_check(sys, OL_F64, n, nullptr, wl, nullptr, 0, s, ~0u));
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  const char* modes[] = {"step", "grid", "refuse", "create"};
+  const char* modes[] = {"step", "grid", "refuse", "create", "rules"};
   int mode = -1;
-  for (int k = 0; k < 4 && argc == 3; ++k)
+  for (int k = 0; k < 5 && argc == 3; ++k)
     if (strcmp(argv[1], modes[k]) == 0) mode = k;
   if (mode < 0) {
-    fprintf(stderr, "usage: hostforbes step|grid|refuse|create <case file>\n");
+    fprintf(stderr, "usage: hostforbes step|grid|refuse|create|rules <case file>\n");
     return 2;
   }
   Case c;
@@ -222,6 +266,7 @@ int main(int argc, char** argv) {
   if (mode == 0) out = c.h[7] ? step<double>(c, v) : step<float>(c, v);
   if (mode == 1) out = c.h[7] ? grid<double>(c, v) : grid<float>(c, v);
   if (mode == 2) out = refuse(c, sys);
+  if (mode == 4) out = rules(c, sys);
   ol_system_destroy(sys);
   return out;
 }

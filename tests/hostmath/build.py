@@ -100,6 +100,52 @@ def build(force: bool = False, verbose: bool = False, sanitize: bool = False) ->
     return lib
 
 
+def build_program(name: str, src: str, force: bool = False, verbose: bool = False,
+                  sanitize: bool = False) -> str:
+    """A stand-alone host checker (tests/hostaim, tests/hostforbes): `src` compiled with the flags
+    above and linked with the two objects this build leaves behind -> `<dir of src>/_build/<name>`
+    (`<name>_asan` with sanitize=True: the sanitizer runtime is linked INTO the program, which
+    runs as an ordinary child process with nothing preloaded)."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    out = os.path.join(os.path.dirname(os.path.abspath(src)), "_build")
+    os.makedirs(out, exist_ok=True)
+    suffix = "_asan" if sanitize else ""
+    exe = os.path.join(out, name + suffix)
+    objs = [os.path.join(OUT, f"{o}{suffix}.o") for o in ("capi", "harness")]
+    # (the SOURCES decide, not the objects: a tree that travels without its object files keeps a
+    # program that is up to date)
+    deps = [os.path.join(CSRC, d) for d in DEPS] + [
+        src, os.path.join(HERE, "harness.hip"), os.path.join(ROOT, "include", "optiland_hip.h"),
+        os.path.abspath(__file__)]
+    if not force and os.path.exists(exe) and \
+            all(os.path.getmtime(d) <= os.path.getmtime(exe) for d in deps):
+        return exe
+    build(force=force, verbose=verbose, sanitize=sanitize)   # capi.o / harness.o up to date
+    if not all(os.path.exists(o) for o in objs):   # (a library that travelled without its objects)
+        build(force=True, verbose=verbose, sanitize=sanitize)
+    flags = ["--offload-host-only", "-std=c++17", "-fPIC", "-ffp-contract=on", "-fno-math-errno",
+             "-Wall"] + (["-mfma"] if _cpu_has_fma() else [])
+    flags += ["-O1", "-g1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+              "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]
+    obj = os.path.join(out, f"main{suffix}.o")
+    cmd = [hipcc, *flags, "-c", src, "-o", obj]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, stderr=None if verbose else subprocess.DEVNULL)
+    if sanitize:
+        clang = os.path.join(os.path.dirname(os.path.realpath(hipcc)), "..", "lib", "llvm", "bin",
+                             "clang++")
+        if not os.path.exists(clang):
+            clang = "/opt/rocm/lib/llvm/bin/clang++"
+        cmd = [clang, "-fsanitize=address,undefined", obj, *objs, "-o", exe]
+    else:
+        cmd = ["g++", obj, *objs, "-o", exe]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return exe
+
+
 if __name__ == "__main__":
     import sys
     print(build(force=True, verbose=True, sanitize="--sanitize" in sys.argv))

@@ -106,6 +106,7 @@ def test_host_step_under_the_sanitizers(tmp_path):
             got, _bits = F.host_step(exe, path)
             F.compare(got[None], c, np.float64 if fp64 else np.float32, lo, hi, rows=[F.FORBES])
         assert "ol_trace: -2" in F.run_host(exe, "refuse", path)
+        assert "good: 0 ok" in F.run_host(exe, "rules", path)
         g = F.grid(c["kind"], "norm12")
         planes = np.zeros((8, g["x"].size))
         planes[0], planes[1] = g["x"], g["y"]
@@ -160,6 +161,47 @@ def test_every_range_walking_entry_refuses_a_forbes_row(hostforbes, tmp_path):
                     "ol_wavefront_reference", "ol_trace_opd_dev", "ol_aim_rays"):
             assert got[who][0] == -2 and "surface 1 is a Forbes surface" in got[who][1], (who, got[who])
         assert got["ol_trace before the row"] == (0, "ok")
+
+
+def test_argument_rules_on_a_host_system(hostforbes, tmp_path):
+    """ol_trace_forbes's host rules (csrc/forbes_host.h) without a device: each text, and the
+    first broken rule answers."""
+    c = F.case("q_norm12_default")
+    lo, hi = c["sets"]["hex127"]
+    path = tmp_path / "rules.case"
+    F.write_case(path, c["table"], c["rows"][0][:, lo:hi])
+    got = _lines(F.run_host(hostforbes, "rules", path))
+    for ok in ("good", "good fp32 midrange", "empty"):
+        assert got[ok] == (0, "ok"), ok
+    who = "ol_trace_forbes: "
+    for what, code, text in (
+            ("null system", -1, "system is NULL"), ("dtype", -1, "bad dtype 5"),
+            ("negative count", -1, "negative ray count"),
+            ("surface -1", -1, "surface -1 outside [0, 4)"),
+            ("surface past the table", -1, "surface 4 outside [0, 4)"),
+            ("not a forbes row", -1, "surface 2 is not a Forbes surface (geometry kind 1): trace it "
+                                     "with ol_trace"),
+            ("wavelength", -1, "wavelength index 1 outside [0, 1)"),
+            ("wavelength -1", -1, "wavelength index -1 outside [0, 1)"),
+            ("flags", -1, "flags 0x4: OL_TRACE_WRITE_RAYS and OL_TRACE_MIDRANGE only"),
+            ("too many", -1, "137438953409 rays are more than one launch takes"),
+            ("null rays", -1, "rays is NULL"), ("null plane", -1, "rays[5] is NULL"),
+            ("stride", -1, "record_stride 126 < n_rays 127"),
+            ("nothing to write", -1, "nothing to write (no record_row, no OL_TRACE_WRITE_RAYS)"),
+            ("all at once", -1, "bad dtype 5"), ("all but dtype", -1, "negative ray count"),
+            ("surface before wavelength", -1, "surface 4 outside [0, 4)"),
+            ("wavelength before flags", -1, "wavelength index -1 outside [0, 1)"),
+            ("flags before planes", -1, "flags 0xffffffff: OL_TRACE_WRITE_RAYS and "
+                                        "OL_TRACE_MIDRANGE only")):
+        assert got[what] == (code, who + text), (what, got[what])
+    # a polarisation-dependent coating on the row: unpolarised launches only
+    coated = S.SystemTable.from_json(c["table"].to_json())
+    coated.surfaces["coating_kind"][F.FORBES] = S.COAT_FRESNEL
+    F.write_case(path, coated, c["rows"][0][:, lo:hi])
+    got = _lines(F.run_host(hostforbes, "rules", path))
+    assert got["good"] == (-2, who + "surface 1 carries a polarisation-dependent coating "
+                                     "(unpolarised launches only)")
+    assert got["flags"][1].startswith(who + "flags 0x4")   # (the flags are looked at first)
 
 
 def test_system_create_validates_forbes_blocks(hostforbes, tmp_path):
