@@ -83,6 +83,18 @@ enum { OL_F32 = 0, OL_F64 = 1 };
  *               ol_trace_opd_dev, ol_wavefront_reference, ol_aim_rays) returns OL_EUNSUPPORTED,
  *               naming the surface, when its range holds one -- a caller cuts the range there.
  *               (Additive: OL_ABI_VERSION is unchanged; look the entry up by name.)
+ * PLANE_GRATING / STANDARD_GRATING
+ *               optiland/geometries/plane_grating.py, standard_grating.py with
+ *               interactions/diffractive_model.py (surface type "grating"): a plane, or the conic
+ *               radius / conic (finite radius, not zero), that diffracts instead of refracting.
+ *               Coefficient block (n_coeff = 3) = {order, period, groove angle}: the diffraction
+ *               order, the groove period in micrometres (finite, not zero; a negative one flips
+ *               the normal term of the direction, as the reference's formula does) and the groove
+ *               orientation angle in radians; ol_system_create adds sin / cos / tan of the angle
+ *               in double.  OL_SURF_REFERENCE_ROOT is honoured on the standard kind.
+ *               Grating rows are traced by ol_trace_grating ONLY, one surface per launch: the
+ *               entry points listed for the Forbes rows return OL_EUNSUPPORTED, naming the
+ *               surface, when their range holds one.  (Additive, like the Forbes kinds.)
  */
 typedef enum ol_geom_kind {
   OL_GEOM_PLANE = 0,
@@ -95,7 +107,9 @@ typedef enum ol_geom_kind {
   OL_GEOM_BICONIC = 7,
   OL_GEOM_TOROIDAL = 8,
   OL_GEOM_FORBES_Q = 9,
-  OL_GEOM_FORBES_Q2D = 10
+  OL_GEOM_FORBES_Q2D = 10,
+  OL_GEOM_PLANE_GRATING = 11,
+  OL_GEOM_STANDARD_GRATING = 12
 } ol_geom_kind;
 
 /* ---- what happens at the surface ----------------------------------------
@@ -404,6 +418,21 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays,
 int ol_trace_forbes(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const rays[8],
                     int32_t wavelength_index, void* record_row, int64_t record_stride,
                     int32_t surface, uint32_t flags, uint32_t* status, void* stream);
+
+/* ONE diffraction grating (OL_GEOM_PLANE_GRATING / OL_GEOM_STANDARD_GRATING) in one launch: what
+ * Surface.trace does there (surfaces/standard_surface.py:232-274 with
+ * interactions/diffractive_model.py:28-61 and rays/real_rays.py:207-522) -- into the surface's
+ * frame, the intersection, propagation, absorption, OPD, aperture clip, the diffraction into the
+ * surface's order (direction normalised; NaN for an evanescent order, the position stays finite),
+ * SimpleCoating, back to the global frame.  Unpolarised only.  Arguments, flags and status as for
+ * ol_trace_forbes, and
+ *   wavelength_um  the wavelength of the bundle in micrometres (finite, > 0): the optics rows
+ *                  carry refractive indices, not the wavelength the grating equation needs
+ *   surface        index of the grating row (OL_EINVAL for any other geometry kind)          */
+int ol_trace_grating(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const rays[8],
+                     int32_t wavelength_index, double wavelength_um, void* record_row,
+                     int64_t record_stride, int32_t surface, uint32_t flags, uint32_t* status,
+                     void* stream);
 
 /* ABI 11.  The iteration count of ONE reference-rule Newton surface for this batch of rays
  * (see OL_SURF_REFERENCE_NEWTON): the rays are traced from `first_surface` up to `surface` --

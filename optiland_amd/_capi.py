@@ -10,6 +10,7 @@ import ctypes as C
 import os
 
 from . import build as _build
+from .system import GEOM_PLANE_GRATING, GEOM_STANDARD_GRATING  # noqa: F401 - OL_GEOM_*_GRATING
 
 _LIB = None
 
@@ -152,6 +153,7 @@ EXPORTS = (
     "ol_mmdft_psf",
     "ol_aim_rays",
     "ol_trace_forbes",
+    "ol_trace_grating",
 )
 
 F32, F64 = 0, 1
@@ -310,6 +312,10 @@ def bind(lib, path: str = "?"):
         lib.ol_trace_forbes.restype = C.c_int
         lib.ol_trace_forbes.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, vp, i64, i32, u32,
                                         vp, vp]
+    if has_trace_grating(lib):   # (additive within ABI 11, like ol_huygens_psf)
+        lib.ol_trace_grating.restype = C.c_int
+        lib.ol_trace_grating.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, C.c_double, vp, i64,
+                                         i32, u32, vp, vp]
     return lib
 
 
@@ -360,6 +366,11 @@ TRACE_MIDRANGE = 0x40                     # OL_TRACE_MIDRANGE
 def has_trace_forbes(lib) -> bool:
     """True when the loaded library exports ol_trace_forbes."""
     return hasattr(lib, "ol_trace_forbes")
+
+
+def has_trace_grating(lib) -> bool:
+    """True when the loaded library exports ol_trace_grating."""
+    return hasattr(lib, "ol_trace_grating")
 
 
 def has_huygens(lib) -> bool:

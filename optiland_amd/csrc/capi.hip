@@ -808,7 +808,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     const ol_surface_desc& s = surf[i];
     HostSurf& d = dev[i];
     std::memset(&d, 0, sizeof(d));
-    if (s.geom_kind < OL_GEOM_PLANE || s.geom_kind > OL_GEOM_FORBES_Q2D)
+    if (s.geom_kind < OL_GEOM_PLANE || s.geom_kind > OL_GEOM_STANDARD_GRATING)
       return failf(OL_EUNSUPPORTED, "surface %d: geometry kind %d", i, s.geom_kind);
     if (s.interaction < OL_INTERACT_RECORD_ONLY || s.interaction > OL_INTERACT_REFLECT)
       return failf(OL_EUNSUPPORTED, "surface %d: interaction %d", i, s.interaction);
@@ -826,15 +826,19 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     d.geom = s.geom_kind;
     if (s.geom_kind == OL_GEOM_FORBES_Q) d.geom = ol::kGeomForbesQ;   // (9 is kGeomZernikeMono)
     if (s.geom_kind == OL_GEOM_FORBES_Q2D) d.geom = ol::kGeomForbesQ2d;
+    if (s.geom_kind == OL_GEOM_PLANE_GRATING) d.geom = ol::kGeomPlaneGrating;
+    if (s.geom_kind == OL_GEOM_STANDARD_GRATING) d.geom = ol::kGeomStandardGrating;
     d.interaction = s.interaction;
     d.aperture_kind = s.aperture_kind;
     d.coating_kind = s.coating_kind;
     d.max_iter = s.max_iter;
     d.poly_cols = s.poly_cols;
     d.flags = (s.flags & OL_SURF_ROTATED) ? ol::kSurfRotated : 0u;
-    const bool inf_r = std::isinf(s.radius) || s.geom_kind == OL_GEOM_PLANE;
+    const bool inf_r = std::isinf(s.radius) || s.geom_kind == OL_GEOM_PLANE ||
+                       s.geom_kind == OL_GEOM_PLANE_GRATING;
     if (inf_r) d.flags |= ol::kSurfRadiusInf;
-    if ((s.flags & OL_SURF_REFERENCE_ROOT) && s.geom_kind == OL_GEOM_STANDARD && !inf_r)
+    if ((s.flags & OL_SURF_REFERENCE_ROOT) && !inf_r &&
+        (s.geom_kind == OL_GEOM_STANDARD || s.geom_kind == OL_GEOM_STANDARD_GRATING))
       d.flags |= ol::kSurfReferenceRoot;
     d.cv = inf_r ? 0.0 : 1.0 / s.radius;
     d.kp1 = 1.0 + s.conic;
@@ -1025,6 +1029,27 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
         dcoef.insert(dcoef.end(), src + 1, src + s.n_coeff);
         for (size_t k : ints) int_slots.push_back(base + k);
       }
+    } else if (ol::is_grating_kind(s.geom_kind)) {
+      // public block {order, period, groove angle} -> device block (grating_device.h)
+      if (s.n_coeff != 3)
+        return failf(OL_EINVAL, "surface %d: a grating needs {order, period, groove angle}", i);
+      if (s.interaction == OL_INTERACT_RECORD_ONLY)
+        return failf(OL_EUNSUPPORTED, "surface %d: a grating that only records", i);
+      if (!std::isfinite(src[1]) || src[1] == 0.0)
+        return failf(OL_EINVAL, "surface %d: grating period %g must be finite and not zero", i,
+                     src[1]);
+      if (!std::isfinite(src[0]) || !std::isfinite(src[2]))
+        return failf(OL_EINVAL, "surface %d: grating order %g / groove angle %g must be finite", i,
+                     src[0], src[2]);
+      if (s.geom_kind == OL_GEOM_STANDARD_GRATING && (inf_r || !(s.radius != 0.0)))
+        return failf(OL_EINVAL, "surface %d: a standard grating needs a finite radius that is not "
+                                "zero (a flat one is OL_GEOM_PLANE_GRATING)", i);
+      d.n_coeff = 3;
+      dcoef.push_back(src[0]);
+      dcoef.push_back(src[1]);
+      dcoef.push_back(std::sin(src[2]));
+      dcoef.push_back(std::cos(src[2]));
+      dcoef.push_back(std::tan(src[2]));
     } else {
       d.n_coeff = 0;
     }
@@ -1063,6 +1088,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     st.ref_newton.push_back((surf[i].flags & OL_SURF_REFERENCE_NEWTON) &&
                                     surf[i].geom_kind != OL_GEOM_PLANE &&
                                     surf[i].geom_kind != OL_GEOM_STANDARD &&
+                                    !ol::is_grating_kind(surf[i].geom_kind) &&
                                     surf[i].interaction != OL_INTERACT_RECORD_ONLY
                                 ? 1 : 0);
   }
@@ -1168,6 +1194,7 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const r
   if (int rc = rule_range("ol_trace", v, first_surface, last_surface)) return rc;
   if (int rc = rule_wavelength("ol_trace", v.n_wl, wavelength_index)) return rc;
   if (int rc = rule_no_forbes("ol_trace", v, first_surface, last_surface)) return rc;
+  if (int rc = rule_no_grating("ol_trace", v, first_surface, last_surface)) return rc;
   if (n_rays == 0) return OL_OK;
   if (int rc = rule_current_device("ol_trace", v)) return rc;
   if (int rc = rule_planes("ol_trace", "rays", rays, 8)) return rc;
@@ -1204,6 +1231,7 @@ int ol_newton_count(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* con
   if (int rc = rule_wavelength("ol_newton_count", v.n_wl, wavelength_index)) return rc;
   if (!iterations) return failf(OL_EINVAL, "ol_newton_count: iterations is NULL");
   if (int rc = rule_no_forbes("ol_newton_count", v, first_surface, surface)) return rc;
+  if (int rc = rule_no_grating("ol_newton_count", v, first_surface, surface)) return rc;
   if (!v.ref_newton[surface])
     return failf(OL_EINVAL, "ol_newton_count: surface %d is not a traced Newton-Raphson surface "
                             "with OL_SURF_REFERENCE_NEWTON", surface);

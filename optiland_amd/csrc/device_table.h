@@ -95,7 +95,11 @@ enum : int {
   // OL_GEOM_FORBES_Q (9) / OL_GEOM_FORBES_Q2D (10) of ol_surface_desc, renumbered: such rows are
   // traced by forbes.hip alone and never reach the fused kernels' dispatch (forbes_device.h)
   kGeomForbesQ = 16,
-  kGeomForbesQ2d = 17
+  kGeomForbesQ2d = 17,
+  // OL_GEOM_PLANE_GRATING (11) / OL_GEOM_STANDARD_GRATING (12), renumbered likewise: traced by
+  // grating.hip alone (grating_device.h); block: {order, period, sin a, cos a, tan a}
+  kGeomPlaneGrating = 18,
+  kGeomStandardGrating = 19
 };
 enum : int { kRecordOnly = 0, kRefract = 1, kReflect = 2 };
 enum : int {

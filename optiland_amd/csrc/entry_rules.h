@@ -103,10 +103,21 @@ inline int rule_no_forbes(const char* who, const SystemView& v, int32_t first, i
   return OL_OK;
 }
 
+// grating rows (OL_GEOM_PLANE_GRATING / _STANDARD_GRATING) likewise: ol_trace_grating alone
+// (grating.hip) diffracts, the fused kernels would refract
+inline int rule_no_grating(const char* who, const SystemView& v, int32_t first, int32_t last) {
+  for (int32_t s = first; s <= last; ++s)
+    if (is_grating_kind(v.geom[s]))
+      return failf(OL_EUNSUPPORTED, "%s: surface %d is a diffraction grating: trace it with "
+                                    "ol_trace_grating and cut the range there", who, s);
+  return OL_OK;
+}
+
 // the fused entry points (one launch: generate -> trace [-> reduce]) walk the whole system and do
 // not serve ranges whose Newton iteration count is a property of the batch
 inline int rule_no_reference_newton(const char* who, const SystemView& v) {
   if (int rc = rule_no_forbes(who, v, 0, v.n_surf - 1)) return rc;
+  if (int rc = rule_no_grating(who, v, 0, v.n_surf - 1)) return rc;
   for (int32_t s = 0; s < v.n_surf; ++s)
     if (v.ref_newton[s])
       return failf(OL_EUNSUPPORTED, "%s: the system carries OL_SURF_REFERENCE_NEWTON surfaces "

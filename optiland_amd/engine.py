@@ -455,8 +455,10 @@ def _start_sweeper() -> None:
 def split_trace(forbes, first: int, last: int, rec, rec_first: int, fused, one) -> None:
     """Walk surfaces [first, last] as fused runs and single Forbes launches, in order.
 
-    forbes: the table's Forbes rows (`SystemTable.forbes`).  rec: the caller's record block or
-    None; its row 0 holds surface `rec_first`.  `fused(a, b, rec_view, rec_from, midrange)` traces
+    forbes: the table's single-launch rows -- `SystemTable.forbes` and, with them,
+    `SystemTable.gratings`: the caller passes the union and tells the two apart in `one` (the
+    parameter keeps its name: callers pass it by position or by this name).  rec: the caller's
+    record block or None; its row 0 holds surface `rec_first`.  `fused(a, b, rec_view, rec_from, midrange)` traces
     the run [a, b] -- `rec_view` is the part of the block whose row 0 is surface `rec_from`, or
     None when the run lies in front of the first recorded surface; `one(s, row, midrange)` traces
     the Forbes surface s (`row`: its (8, stride) row of the block, or None).  Both carry the ray
@@ -807,9 +809,10 @@ class HipSystem:
               defer_status: bool = False, zero_status: bool = True,
               spot=None, record_first: int | None = None,
               nonunit_directions: bool = False, _status_to=None) -> TraceResult:
-        """Launch the fused trace.  A range that holds Forbes rows (`table.forbes`) is split into
-        fused runs and one `trace_forbes` launch per such row, all writing into the same record
-        block and status word (unpolarised, no spot epilogue).
+        """Launch the fused trace.  A range that holds Forbes rows (`table.forbes`) or grating
+        rows (`table.gratings`) is split into fused runs and one `trace_forbes` / `trace_grating`
+        launch per such row, all writing into the same record block and status word (unpolarised,
+        no spot epilogue).
 
         rays: sequence of 8 contiguous 1-D device tensors (x,y,z,L,M,N,i,opd) of one
         dtype -- the initial state.  record: True (allocate), False/None, or a
@@ -854,10 +857,11 @@ class HipSystem:
                 raise ValueError("record must be a contiguous (rows, 8, stride>=n) tensor")
         if write_rays is None:
             write_rays = rec is None
-        if self.table.forbes and any(first <= f <= last for f in self.table.forbes):
+        singles = self.table.forbes + self.table.gratings
+        if singles and any(first <= f <= last for f in singles):
             if prt is not None or spot is not None:
-                raise ValueError("a range with Forbes surfaces is traced unpolarised and without "
-                                 "the spot epilogue (cut it at those surfaces)")
+                raise ValueError("a range with Forbes surfaces or gratings is traced unpolarised "
+                                 "and without the spot epilogue (cut it at those surfaces)")
             return self._trace_split(rays, int(wavelength_index), rec, rec_first, int(first),
                                      int(last), write_rays, check_status, defer_status,
                                      zero_status)
@@ -936,6 +940,37 @@ class HipSystem:
         the status word (0 when deferred or unchecked).  A missing kernel is an error."""
         if not self.can_trace_forbes():
             raise _capi.HipExtensionError("the loaded library has no ol_trace_forbes: rebuild it")
+        return self._trace_single("ol_trace_forbes", (), self.table.forbes, "a Forbes", rays,
+                                  surface, wavelength_index,
+                                  record_row, write_rays, midrange, check_status, defer_status,
+                                  zero_status)
+
+    # ---- diffraction gratings (ol_trace_grating: one surface, one launch) ---------------------
+    def can_trace_grating(self) -> bool:
+        return _capi.has_trace_grating(self.lib)
+
+    def trace_grating(self, rays, surface: int, wavelength_index: int = 0, record_row=None,
+                      write_rays: bool | None = None, midrange: bool = False,
+                      check_status: bool = True, defer_status: bool = False,
+                      zero_status: bool = True) -> int:
+        """`trace_forbes` for the ONE grating row `surface` of the table (`ol_trace_grating`):
+        frame change, intersection, diffraction into the surface's order at the wavelength
+        `table.wavelengths[wavelength_index]`, back to the global frame.  An evanescent order
+        leaves a finite position and a NaN direction (STATUS_NAN_DIRECTION unless midrange).  A
+        missing kernel is an error."""
+        if not self.can_trace_grating():
+            raise _capi.HipExtensionError("the loaded library has no ol_trace_grating: rebuild it")
+        wl = float(self.table.wavelengths[int(wavelength_index)])
+        return self._trace_single("ol_trace_grating", (wl,), self.table.gratings, "a grating",
+                                  rays, surface, wavelength_index,
+                                  record_row, write_rays, midrange, check_status, defer_status,
+                                  zero_status)
+
+    def _trace_single(self, entry, extra, rows, kind, rays, surface, wavelength_index, record_row,
+                      write_rays, midrange, check_status, defer_status, zero_status) -> int:
+        """The launch `trace_forbes` and `trace_grating` share: `entry` takes `extra` behind the
+        wavelength index and serves the table's `rows` ("`kind` row"), everything else alike --
+        the checks in the order `trace_forbes` always made them."""
         rays = list(rays)
         if len(rays) != 8:
             raise ValueError("rays must be 8 planes: x,y,z,L,M,N,i,opd")
@@ -946,8 +981,8 @@ class HipSystem:
         for t in rays:
             if t.device != self.device or t.dtype != dtype or t.numel() != n or not t.is_contiguous():
                 raise ValueError("ray planes must be contiguous, same dtype/size, on the system's device")
-        if int(surface) not in self.table.forbes:
-            raise ValueError(f"surface {surface} is not a Forbes row of this table")
+        if int(surface) not in rows:
+            raise ValueError(f"surface {surface} is not {kind} row of this table")
         row = record_row
         if row is not None:
             if row.dtype != dtype or row.dim() != 2 or row.shape[0] != 8 or row.shape[1] < n \
@@ -962,20 +997,20 @@ class HipSystem:
         if check_status and zero_status:
             self._status.zero_()
         with self._device_ctx():
-            rc = self.lib.ol_trace_forbes(
-                self._handle, _DT[dtype], n, ptrs, int(wavelength_index),
+            rc = getattr(self.lib, entry)(
+                self._handle, _DT[dtype], n, ptrs, int(wavelength_index), *extra,
                 row.data_ptr() if row is not None else None,
                 int(row.shape[1]) if row is not None else 0, int(surface), flags,
                 self._status.data_ptr() if check_status else None, self._stream())
-        self._check(rc, "ol_trace_forbes")
+        self._check(rc, entry)
         status = int(self._status.item()) if (check_status and not defer_status) else 0
         self.raise_for_status(status)
         return status
 
     def _trace_split(self, rays, wl, rec, rec_first, first, last, write_rays, check_status,
                      defer_status, zero_status) -> TraceResult:
-        """`trace` over a range with Forbes rows (`split_trace`).  The state travels in `rays`
-        themselves (write_rays) or in a private copy of them; every launch ORs into the one
+        """`trace` over a range with Forbes or grating rows (`split_trace`).  The state travels in
+        `rays` themselves (write_rays) or in a private copy of them; every launch ORs into the one
         status word, except that what a fused run in FRONT of a later launch reports about its
         own last surface (STATUS_NAN_DIRECTION) is dropped: it is not the end of this trace."""
         n = int(rays[0].numel())
@@ -995,11 +1030,15 @@ class HipSystem:
                        zero_status=False, record_first=r0 if (r0 is not None and r0 != a) else None,
                        _status_to=word)
 
-        def one(s, row, midrange):
-            self.trace_forbes(work, s, wl, record_row=row, write_rays=True, midrange=midrange,
-                              check_status=check_status, defer_status=True, zero_status=False)
+        gratings = set(self.table.gratings)
 
-        split_trace(self.table.forbes, first, last, rec, rec_first, fused, one)
+        def one(s, row, midrange):
+            launch = self.trace_grating if s in gratings else self.trace_forbes
+            launch(work, s, wl, record_row=row, write_rays=True, midrange=midrange,
+                   check_status=check_status, defer_status=True, zero_status=False)
+
+        split_trace(self.table.forbes + self.table.gratings, first, last, rec, rec_first, fused,
+                    one)
         if mid:
             self._status.bitwise_or_(mid[0].bitwise_and_(~S.STATUS_NAN_DIRECTION))
         status = int(self._status.item()) if (check_status and not defer_status) else 0

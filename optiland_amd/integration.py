@@ -956,7 +956,9 @@ def _make_tracer_class():
 # --------------------------------------------------------------------------------------
 # SurfaceGroup.trace(rays, skip) -- the seam for callers that bring their own rays
 # --------------------------------------------------------------------------------------
-_SG = {"device": None, "force": False, "count": 0, "fallbacks": 0, "foreign": 0}
+_SG = {"device": None, "force": False, "count": 0, "fallbacks": 0, "foreign": 0,
+       # enable(gratings=...): diffraction gratings as device work (OPTILAND_HIP_GRATINGS=0: off)
+       "gratings": os.environ.get("OPTILAND_HIP_GRATINGS", "1") != "0"}
 # settings of the class-wide patch (enable())
 _ENABLE = {"device": None, "force": False, "lazy": False}
 _PLANE_ATTRS = ("x", "y", "z", "L", "M", "N", "i", "opd")
@@ -998,21 +1000,30 @@ def _sg_table(group, wavelength):
     """`pack_surfaces(group.surfaces, tolerate=True)`, memoised on the group against the
     change-detector token of its surfaces (fingerprint.py): a caller that pushes bundle
     after bundle through an unchanged SurfaceGroup packs it once.  None = the fused path
-    refuses the whole group."""
+    refuses the whole group.
+
+    Grating rows are packed as such (`table.gratings`) only when the engine factory in use
+    declares that its engines trace them (`tracer._make_engine.traces_gratings`) and
+    `enable(gratings=False)` / OPTILAND_HIP_GRATINGS=0 has not switched them off: decided HERE,
+    before packing, so that the production path packs once and a stand-in factory that knows
+    nothing of gratings gets the table -- and the reference's own surface -- it always got."""
+    gratings = bool(_SG["gratings"]) and bool(getattr(_tracer._make_engine, "traces_gratings",
+                                                      False))
     tok = None
     if _fp.ENABLED:
         tok, _keep = _fp.surfaces_token(group.surfaces, wavelength)
         memo = group.__dict__.get("_hip_sg_memo")
         memo = memo.value if memo is not None else None
-        if memo is not None and memo[0] == tok:
+        if memo is not None and memo[0] == tok and memo[3] == gratings:
             return memo[2]
     try:
-        table = pack_surfaces(group.surfaces, [wavelength], name="SurfaceGroup", tolerate=True)
+        table = pack_surfaces(group.surfaces, [wavelength], name="SurfaceGroup", tolerate=True,
+                              gratings=gratings)
     except UnsupportedSystem:
         table = None
     if tok is not None:
         tok, keep = _fp.surfaces_token(group.surfaces, wavelength)  # after the pack
-        group.__dict__["_hip_sg_memo"] = _Volatile((tok, keep, table))
+        group.__dict__["_hip_sg_memo"] = _Volatile((tok, keep, table, gratings))
     return table
 
 
@@ -1105,7 +1116,7 @@ def _hip_surface_group_trace(group, rays, skip):
     (interactions/refractive_reflective_model.py:41) and PolarizedRays.p is advanced
     from its CURRENT value (rays/polarized_rays.py:180-202).
 
-    Surfaces the fused path does not implement (thin lens, grating, phase, NURBS
+    Surfaces the fused path does not implement (thin lens, phase, NURBS
     / grid-sag geometry, GRIN media, BSDF, thin-film coating ...) do not disqualify the
     whole system: they are traced by their own `Surface.trace(rays)` on the same device
     tensors, and the runs of supported surfaces between them are one launch each
@@ -1118,7 +1129,13 @@ def _hip_surface_group_trace(group, rays, skip):
     ForbesQ2dGeometry) are device work too: inside a run they are one `ol_trace_forbes` launch
     between two fused launches (`HipSystem.trace` splits the range), and they count as served
     when the seam decides whether anything would run on the device at all.  A POLARISED bundle
-    takes the reference's own surface there, as before (that kernel is unpolarised)."""
+    takes the reference's own surface there, as before (that kernel is unpolarised).
+
+    Diffraction gratings (`table.gratings`: PlaneGrating / StandardGratingGeometry with
+    DiffractiveInteractionModel) are the same: one `ol_trace_grating` launch inside a run, served,
+    a polarised bundle excepted.  They are in the table only when the engine that will trace it
+    can trace them and `enable(gratings=False)` has not switched them off (`_sg_table`);
+    otherwise the surface is in `table.unsupported` and the reference's own, as before."""
     import optiland.backend as be
     from optiland.rays import PolarizedRays as RefPolarizedRays
     from optiland.rays import RealRays as RefRealRays
@@ -1142,7 +1159,7 @@ def _hip_surface_group_trace(group, rays, skip):
         return None
     foreign = set(table.unsupported)
     if polarized:
-        foreign |= set(table.forbes)
+        foreign |= set(table.forbes) | set(table.gratings)
     if len(foreign) >= n_s - skip - (1 if skip == 0 else 0):
         return None  # nothing but the object row would run fused
     if table.uses_polarization and not polarized:
@@ -1314,7 +1331,7 @@ def _set_reference_newton(reference_newton):
 
 
 def enable(device=None, force=False, analyses=True, lazy_records=False, placed_records=None,
-           reference_root=None, reference_newton=None):
+           reference_root=None, reference_newton=None, gratings=None):
     """Route EVERY `Optic` (existing and future) through the HIP path.
 
     Patches `RealRayTracer.trace / trace_generic` (raytrace/real_ray_tracer.py:58-154)
@@ -1367,10 +1384,17 @@ def enable(device=None, force=False, analyses=True, lazy_records=False, placed_r
     counting launch per Newton surface and one verifying launch per trace call, and the fused
     analysis kernels stand back for such optics (the reference's own analysis code then runs on
     top of the drop-in's `Optic.trace`).
+
+    `gratings` (default on; None = leave as is, OPTILAND_HIP_GRATINGS=0 seeds it off): diffraction
+    gratings (surface type "grating") are one `ol_trace_grating` launch between two fused runs.
+    False: they are traced by the reference's own `Surface.trace`, as every surface the fused
+    path does not know.
     """
     _set_record_pool(placed_records)
     _set_reference_root(reference_root)
     _set_reference_newton(reference_newton)
+    if gratings is not None:
+        _SG["gratings"] = bool(gratings)
     cls = _make_tracer_class()
     from optiland.raytrace.real_ray_tracer import RealRayTracer
 

@@ -225,7 +225,55 @@ def _pack_forbes(geom, row, coeffs: list, classes) -> None:
     coeffs.extend(block)
 
 
-def _pack_geometry(geom, row, coeffs: list, forbes: bool = False):
+def _grating_classes():
+    """(PlaneGrating, StandardGratingGeometry, DiffractiveInteractionModel) of the reference, or
+    None where it has none.  Gratings are recognised by `isinstance` against these."""
+    try:
+        from optiland.geometries.plane_grating import PlaneGrating
+        from optiland.geometries.standard_grating import StandardGratingGeometry
+        from optiland.interactions.diffractive_model import DiffractiveInteractionModel
+    except Exception:  # noqa: BLE001 - a reference without gratings
+        return None
+    return PlaneGrating, StandardGratingGeometry, DiffractiveInteractionModel
+
+
+def _is_grating(surf) -> bool:
+    """A PlaneGrating / StandardGratingGeometry WITH the diffractive interaction model."""
+    classes = _grating_classes()
+    return classes is not None and isinstance(surf.geometry, classes[:2]) \
+        and isinstance(surf.interaction_model, classes[2])
+
+
+def _pack_grating(geom, row, coeffs: list) -> None:
+    """A diffraction grating in full (tolerate mode only): the block {order, period, groove
+    angle} of OL_GEOM_PLANE_GRATING / OL_GEOM_STANDARD_GRATING (include/optiland_hip.h).  Raises
+    `UnsupportedSystem` for what stays with the reference's own surface: a period that is not
+    finite or zero (the factory default is inf, which makes the reference's own formula NaN), an
+    order that is not a whole number, a curved grating without a finite radius."""
+    if S.OPTIONS["reference_newton"]:
+        raise UnsupportedSystem("grating under the reference Newton rule")
+    order, period = _f(geom.grating_order), _f(geom.grating_period)
+    angle = _f(geom.groove_orientation_angle)
+    if not math.isfinite(period) or period == 0.0:
+        raise UnsupportedSystem(f"grating period {period!r}")
+    if not math.isfinite(order) or order != math.floor(order):
+        raise UnsupportedSystem(f"grating order {order!r} is not a whole number")
+    if not math.isfinite(angle):
+        raise UnsupportedSystem(f"groove orientation angle {angle!r}")
+    if isinstance(geom, _grating_classes()[0]):
+        row["geom_kind"] = S.GEOM_PLANE_GRATING
+    else:
+        radius = _f(geom.radius)
+        if not math.isfinite(radius) or radius == 0.0:
+            raise UnsupportedSystem(f"curved grating of radius {radius!r}")
+        row["geom_kind"] = S.GEOM_STANDARD_GRATING
+        row["radius"] = radius
+        row["conic"] = _f(geom.k)
+    row["n_coeff"] = 3
+    coeffs.extend([order, period, angle])
+
+
+def _pack_geometry(geom, row, coeffs: list, forbes: bool = False, grating: bool = False):
     name = type(geom).__name__
     row["coeff_offset"] = len(coeffs)
     row["n_coeff"] = 0
@@ -234,6 +282,9 @@ def _pack_geometry(geom, row, coeffs: list, forbes: bool = False):
     row["tol"] = 0.0
     row["max_iter"] = 0
     row["norm_radius"] = 1.0
+    if grating:   # (the caller saw the classes: `_is_grating`)
+        _pack_grating(geom, row, coeffs)
+        return
     if name == "Plane":
         row["geom_kind"] = S.GEOM_PLANE
         return
@@ -448,11 +499,16 @@ def _is_forbes_row(row) -> bool:
     return int(row["geom_kind"]) in (S.GEOM_FORBES_Q, S.GEOM_FORBES_Q2D)
 
 
-def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False):
+def _is_grating_row(row) -> bool:
+    return int(row["geom_kind"]) in (S.GEOM_PLANE_GRATING, S.GEOM_STANDARD_GRATING)
+
+
+def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, gratings: bool = False):
     """One surface, packed by itself: (desc row, its coefficient block as a list with every
     offset RELATIVE to the block, optics rows per wavelength).  Raises `UnsupportedSystem`.
     forbes: a Forbes surface is packed as a row of its own kind (`pack_surfaces(tolerate=True)`)
-    instead of raising."""
+    instead of raising; gratings: so is a diffraction grating (`pack_surfaces(tolerate=True,
+    gratings=True)`)."""
     row = np.zeros((), dtype=S.SURFACE_DESC_DTYPE)
     opt = np.zeros(wl.size, dtype=S.SURFACE_OPTICS_DTYPE)
     coeffs: list = []
@@ -464,13 +520,14 @@ def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False):
     if S.OPTIONS["reference_root"]:   # (the C side honours it on curved standard surfaces only)
         row["flags"] |= S.SURF_REFERENCE_ROOT
     im = surf.interaction_model
-    if type(im).__name__ != "RefractiveReflectiveModel":
+    grating = gratings and not is_object and _is_grating(surf)
+    if type(im).__name__ != "RefractiveReflectiveModel" and not grating:
         raise UnsupportedSystem(
             f"interaction model {type(im).__name__} is not on the fused path"
         )
     if getattr(im, "bsdf", None) is not None:
         raise UnsupportedSystem("BSDF scatter is not on the fused path")
-    _pack_geometry(geom, row, coeffs, forbes and not is_object)
+    _pack_geometry(geom, row, coeffs, forbes and not is_object, grating)
     if S.OPTIONS["reference_newton"] and int(row["geom_kind"]) not in (S.GEOM_PLANE,
                                                                       S.GEOM_STANDARD):
         # the reference's batch-global stop rule on this Newton-Raphson surface (opt-in)
@@ -479,6 +536,8 @@ def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False):
     _pack_coating(surf.coating, row, coeffs)
     if _is_forbes_row(row) and int(row["coating_kind"]) >= S.COAT_FRESNEL:
         raise UnsupportedSystem("polarisation-dependent coating on a Forbes surface")
+    if grating and int(row["coating_kind"]) >= S.COAT_FRESNEL:
+        raise UnsupportedSystem("polarisation-dependent coating on a grating")
     if is_object:
         # ObjectSurface.trace only records (surfaces/object_surface.py:56-93)
         row["interaction"] = S.INTERACT_RECORD_ONLY
@@ -540,7 +599,7 @@ def _relocate(row, local: list, base: int):
 
 def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
                   tolerate: bool = False, tokens=None, cache: dict | None = None,
-                  keep=None) -> SystemTable:
+                  keep=None, gratings: bool = False) -> SystemTable:
     """Flatten a sequence of reference `Surface` objects (a `SurfaceGroup`'s list) for
     the given wavelengths (microns): everything `SurfaceGroup.trace`
     (surfaces/surface_group.py:245-257) needs -- no ray-generator scalars, no
@@ -554,7 +613,12 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
     Forbes surface (the reference's ForbesQNormalSlopeGeometry / ForbesQbfsGeometry /
     ForbesQ2dGeometry, by `isinstance`) is packed in full as a row of its own kind and listed in
     `table.forbes`, not in `table.unsupported`: one `ol_trace_forbes` launch between two fused
-    runs (`HipSystem.trace`).  Strict packing keeps raising for it.
+    runs (`HipSystem.trace`).  Strict packing keeps raising for it.  With `tolerate` AND
+    `gratings` (the caller's engine can trace them: `HipSystem.can_trace_grating`), a diffraction
+    grating (PlaneGrating / StandardGratingGeometry with DiffractiveInteractionModel, by
+    `isinstance`) is packed likewise and listed in `table.gratings`; without `gratings` it stays
+    in `table.unsupported`, and so does one the kernel does not serve (`_pack_grating`, a BSDF, a
+    Jones coating, an inhomogeneous medium).
 
     `tokens` + `cache` (both or neither): per-surface change-detector tokens
     (fingerprint.surface_token, i.e. element [1] of `optic_token`) and a dict the caller
@@ -606,9 +670,14 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
                 packed = hit[1]
                 if not tolerate and _is_forbes_row(packed[0]):   # (cached by a tolerant pack)
                     raise UnsupportedSystem("Forbes geometry is not on the fused path")
+                if _is_grating_row(packed[0]) and not (tolerate and gratings):
+                    if not tolerate:
+                        raise UnsupportedSystem("a grating is not on the fused path")
+                    packed = None   # (cached by a pack that served gratings: decided below)
         if packed is None:
             try:
-                packed = _pack_surface_local(i == 0, surf, wl, forbes=tolerate)
+                packed = _pack_surface_local(i == 0, surf, wl, forbes=tolerate,
+                                             gratings=tolerate and gratings)
             except UnsupportedSystem:
                 if not tolerate or i == 0:
                     raise
@@ -637,7 +706,7 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
     )
     table.last_thickness = _f(surfaces[-1].thickness) if n_s else 0.0
     table.unsupported = tuple(unsupported)
-    if use_cache and not unsupported and not table.forbes:
+    if use_cache and not unsupported and not table.forbes and not table.gratings:
         cache["assembled"] = (tuple(id(s_) for s_ in surfaces), wl_key, list(tokens), bases,
                               table)
     return table

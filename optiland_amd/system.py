@@ -27,6 +27,8 @@ GEOM_ODD_ASPHERE, GEOM_POLYNOMIAL = 4, 5
 GEOM_CHEBYSHEV, GEOM_BICONIC, GEOM_TOROIDAL = 6, 7, 8
 # Forbes surfaces: one launch of their own each (ol_trace_forbes), never inside a fused range
 GEOM_FORBES_Q, GEOM_FORBES_Q2D = 9, 10
+# diffraction gratings likewise (ol_trace_grating); block: {order, period (um), groove angle}
+GEOM_PLANE_GRATING, GEOM_STANDARD_GRATING = 11, 12
 INTERACT_RECORD_ONLY, INTERACT_REFRACT, INTERACT_REFLECT = 0, 1, 2
 AP_NONE, AP_RADIAL, AP_OFFSET_RADIAL, AP_RECTANGULAR, AP_ELLIPTICAL = 0, 1, 2, 3, 4
 AP_COMPOSITE = 5
@@ -71,6 +73,8 @@ GEOM_NAMES = {
     GEOM_TOROIDAL: "toroidal",
     GEOM_FORBES_Q: "forbes_q",
     GEOM_FORBES_Q2D: "forbes_q2d",
+    GEOM_PLANE_GRATING: "plane_grating",
+    GEOM_STANDARD_GRATING: "standard_grating",
 }
 
 # numpy image of `ol_surface_desc`; align=True reproduces the C layout.
@@ -196,6 +200,18 @@ class SystemTable:
                 int(i) for i in np.nonzero((g == GEOM_FORBES_Q) | (g == GEOM_FORBES_Q2D))[0])
         return memo
 
+    @property
+    def gratings(self) -> tuple:
+        """Indices of the grating rows (GEOM_PLANE_GRATING / GEOM_STANDARD_GRATING): each is one
+        `ol_trace_grating` launch between two fused runs, like the Forbes rows."""
+        memo = self.__dict__.get("_gratings")
+        if memo is None:
+            g = self.surfaces["geom_kind"]
+            memo = self.__dict__["_gratings"] = tuple(
+                int(i) for i in np.nonzero((g == GEOM_PLANE_GRATING)
+                                           | (g == GEOM_STANDARD_GRATING))[0])
+        return memo
+
     def reference_newton_surfaces(self, first: int = 0, last: int | None = None) -> list:
         """Traced Newton-Raphson surfaces of [first, last] that carry SURF_REFERENCE_NEWTON (the
         reference's batch-global stop rule, newton_raphson.py:137-166): their iteration count is
@@ -207,6 +223,8 @@ class SystemTable:
                 int(i) for i in np.nonzero((s["flags"] & SURF_REFERENCE_NEWTON != 0)
                                            & (s["geom_kind"] != GEOM_PLANE)
                                            & (s["geom_kind"] != GEOM_STANDARD)
+                                           & (s["geom_kind"] != GEOM_PLANE_GRATING)
+                                           & (s["geom_kind"] != GEOM_STANDARD_GRATING)
                                            & (s["interaction"] != INTERACT_RECORD_ONLY))[0]]
         if not memo:
             return memo

@@ -36,6 +36,13 @@ def _make_engine(table: SystemTable, device):
     return HipSystem(table, device)
 
 
+# What the drop-in's SurfaceGroup seam asks of the factory IN USE before it packs
+# (integration._sg_table): only a factory that declares it gets grating rows packed as such
+# (`pack_surfaces(gratings=True)`); a replacement that says nothing gets the table without them
+# and the reference's own surface there.
+_make_engine.traces_gratings = True
+
+
 class RecordedSurfaces:
     """Stacked per-surface state of the last trace: `(S+1, N)` views (no copy).
 
