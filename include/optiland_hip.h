@@ -95,6 +95,29 @@ enum { OL_F32 = 0, OL_F64 = 1 };
  *               Grating rows are traced by ol_trace_grating ONLY, one surface per launch: the
  *               entry points listed for the Forbes rows return OL_EUNSUPPORTED, naming the
  *               surface, when their range holds one.  (Additive, like the Forbes kinds.)
+ * PLANE_PHASE   optiland/geometries/plane.py with interactions/phase_interaction_model.py (a
+ *               metalens, a diffractive or holographic element): a plane whose interaction adds
+ *               the gradient of a phase profile (optiland/phase/) to the tangential wave vector.
+ *               The coefficient block describes itself; all values are doubles, counts are whole
+ *               numbers stored as doubles:
+ *                 [0] profile kind   0 constant, 1 linear, 2 radial, 3 grid
+ *                 [1] efficiency     the profile's efficiency (finite): a factor of the intensity
+ *                 constant: [2] phase (rad)
+ *                 linear:   [2] K_x  [3] K_y   (rad / mm) order * 2 pi / period * (cos, sin)(angle)
+ *                 radial:   [2] count, then a_2, a_4, ...       phi = sum a_2p r^2p  (rad, r in mm)
+ *                 grid:     [2] W  [3] H  [4] xmin  [5] xmax  [6] ymin  [7] ymax  [8] n_scale,
+ *                           then n_scale scales, then H * W node values, row-major, row = y index
+ *               W, H >= 2; the four bounds are finite, xmax != xmin, ymax != ymin; the node
+ *               (col, row) lies at (xmin + col (xmax - xmin) / (W - 1), ymin + row ...).  The
+ *               interpolant is torch's grid_sample(mode="bilinear", align_corners=True,
+ *               padding_mode="zeros") with its exact derivative: a neighbour outside the grid
+ *               counts as 0.  n_scale is 0 (phase values in radians: GridPhaseProfile) or the
+ *               wavelength count of the table (HeightProfile: the nodes are heights in mm and
+ *               scale[j] = 2 pi / (lambda_j * 1e-3) * (n_material(lambda_j) - 1)); the kernel takes
+ *               scale[wavelength_index].  Counts must add up to n_coeff exactly.
+ *               Phase rows are traced by ol_trace_phase ONLY, one surface per launch: the entry
+ *               points listed for the Forbes rows return OL_EUNSUPPORTED, naming the surface,
+ *               when their range holds one.  (Additive, like the Forbes kinds.)
  */
 typedef enum ol_geom_kind {
   OL_GEOM_PLANE = 0,
@@ -109,7 +132,9 @@ typedef enum ol_geom_kind {
   OL_GEOM_FORBES_Q = 9,
   OL_GEOM_FORBES_Q2D = 10,
   OL_GEOM_PLANE_GRATING = 11,
-  OL_GEOM_STANDARD_GRATING = 12
+  OL_GEOM_STANDARD_GRATING = 12,
+  /* 13 is not a kind: ol_system_create has always refused it as unknown and still does */
+  OL_GEOM_PLANE_PHASE = 14
 } ol_geom_kind;
 
 /* ---- what happens at the surface ----------------------------------------
@@ -433,6 +458,21 @@ int ol_trace_grating(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* co
                      int32_t wavelength_index, double wavelength_um, void* record_row,
                      int64_t record_stride, int32_t surface, uint32_t flags, uint32_t* status,
                      void* stream);
+
+/* ONE phase-profile plane (OL_GEOM_PLANE_PHASE) in one launch: what Surface.trace does there
+ * (surfaces/standard_surface.py:232-274 with interactions/phase_interaction_model.py:45-132) --
+ * into the surface's frame, the plane hit, propagation, absorption, OPD, aperture clip, the
+ * gradient of the phase added to the tangential wave vector (direction normalised; an evanescent
+ * ray gets intensity 0 and a finite direction along the surface, and raises no status bit), the
+ * phase taken off the optical path, SimpleCoating, the profile's efficiency, back to the global
+ * frame.  Unpolarised only.  Arguments, flags and status as for ol_trace_grating:
+ *   wavelength_index  also selects the scale of a height-profile grid
+ *   wavelength_um     the wavelength of the bundle in micrometres (finite, > 0)
+ *   surface           index of the phase row (OL_EINVAL for any other geometry kind)          */
+int ol_trace_phase(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const rays[8],
+                   int32_t wavelength_index, double wavelength_um, void* record_row,
+                   int64_t record_stride, int32_t surface, uint32_t flags, uint32_t* status,
+                   void* stream);
 
 /* ABI 11.  The iteration count of ONE reference-rule Newton surface for this batch of rays
  * (see OL_SURF_REFERENCE_NEWTON): the rays are traced from `first_surface` up to `surface` --

@@ -11,6 +11,7 @@ import os
 
 from . import build as _build
 from .system import GEOM_PLANE_GRATING, GEOM_STANDARD_GRATING  # noqa: F401 - OL_GEOM_*_GRATING
+from .system import GEOM_PLANE_PHASE  # noqa: F401 - OL_GEOM_PLANE_PHASE
 
 _LIB = None
 
@@ -154,6 +155,7 @@ EXPORTS = (
     "ol_aim_rays",
     "ol_trace_forbes",
     "ol_trace_grating",
+    "ol_trace_phase",
 )
 
 F32, F64 = 0, 1
@@ -316,6 +318,10 @@ def bind(lib, path: str = "?"):
         lib.ol_trace_grating.restype = C.c_int
         lib.ol_trace_grating.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, C.c_double, vp, i64,
                                          i32, u32, vp, vp]
+    if has_trace_phase(lib):   # (additive within ABI 11, like ol_trace_grating)
+        lib.ol_trace_phase.restype = C.c_int
+        lib.ol_trace_phase.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, C.c_double, vp, i64,
+                                       i32, u32, vp, vp]
     return lib
 
 
@@ -371,6 +377,11 @@ def has_trace_forbes(lib) -> bool:
 def has_trace_grating(lib) -> bool:
     """True when the loaded library exports ol_trace_grating."""
     return hasattr(lib, "ol_trace_grating")
+
+
+def has_trace_phase(lib) -> bool:
+    """True when the loaded library exports ol_trace_phase."""
+    return hasattr(lib, "ol_trace_phase")
 
 
 def has_huygens(lib) -> bool:

@@ -790,6 +790,75 @@ int ol_set_tuning(int32_t knob, int32_t value) {
 }
 
 namespace {
+// The self-describing block of an OL_GEOM_PLANE_PHASE row (ol_geom_kind in optiland_hip.h), checked
+// value by value and appended to `out` in the layout phase_device.h reads.  src: the row's
+// s.n_coeff values (inside the buffer: the caller checked the range).
+int stage_phase_block(int32_t i, const ol_surface_desc& s, const double* src, int32_t n_wl,
+                      std::vector<double>& out, std::vector<size_t>& int_slots) {
+  const int64_t n = s.n_coeff;
+  // a count stored as a double: whole, not negative, no larger than the block itself
+  auto whole = [&](double c, int64_t& v) {
+    if (!(c >= 0.0) || c > (double)n || c != std::floor(c)) return false;
+    v = (int64_t)c;
+    return true;
+  };
+  if (s.interaction == OL_INTERACT_RECORD_ONLY)
+    return failf(OL_EUNSUPPORTED, "surface %d: a phase surface that only records", i);
+  int64_t kind = 0;
+  if (n < 2 || !whole(src[0], kind) || kind > 3)
+    return failf(OL_EINVAL, "surface %d: phase profile kind %g is not 0 (constant), 1 (linear), "
+                            "2 (radial) or 3 (grid)", i, n >= 1 ? src[0] : -1.0);
+  if (!std::isfinite(src[1]))
+    return failf(OL_EINVAL, "surface %d: phase profile efficiency %g must be finite", i, src[1]);
+  const size_t base = out.size();
+  int_slots.push_back(base);
+  if (kind == ol::kPhaseConstant || kind == ol::kPhaseLinear) {
+    const int64_t need = kind == ol::kPhaseConstant ? 3 : 4;
+    if (n != need)
+      return failf(OL_EINVAL, "surface %d: a %s phase block holds %lld values, not %lld", i,
+                   kind == ol::kPhaseConstant ? "constant" : "linear", (long long)need,
+                   (long long)n);
+    out.insert(out.end(), src, src + n);
+    return OL_OK;
+  }
+  if (kind == ol::kPhaseRadial) {
+    int64_t count = 0;
+    if (n < 3 || !whole(src[2], count) || 3 + count != n)
+      return failf(OL_EINVAL, "surface %d: radial phase block of %lld values does not match the "
+                              "term count %g it declares", i, (long long)n, n >= 3 ? src[2] : -1.0);
+    int_slots.push_back(base + 2);
+    out.insert(out.end(), src, src + n);
+    return OL_OK;
+  }
+  int64_t W = 0, H = 0, n_scale = 0;
+  if (n < 9 || !whole(src[2], W) || !whole(src[3], H) || W < 2 || H < 2)
+    return failf(OL_EINVAL, "surface %d: a phase grid needs whole node counts W, H >= 2 (got %g, "
+                            "%g)", i, n >= 9 ? src[2] : -1.0, n >= 9 ? src[3] : -1.0);
+  for (int k = 4; k < 8; ++k)
+    if (!std::isfinite(src[k]))
+      return failf(OL_EINVAL, "surface %d: phase grid bound %g is not finite", i, src[k]);
+  if (src[5] == src[4] || src[7] == src[6])
+    return failf(OL_EINVAL, "surface %d: phase grid bounds coincide (x %g .. %g, y %g .. %g)", i,
+                 src[4], src[5], src[6], src[7]);
+  if (!whole(src[8], n_scale) || (n_scale != 0 && n_scale != n_wl))
+    return failf(OL_EINVAL, "surface %d: phase grid scale count %g is neither 0 nor the "
+                            "wavelength count %d", i, src[8], n_wl);
+  if (9 + n_scale + W * H != n)
+    return failf(OL_EINVAL, "surface %d: phase grid block of %lld values does not match the "
+                            "counts it declares (9 + %lld scales + %lld x %lld nodes)", i,
+                 (long long)n, (long long)n_scale, (long long)W, (long long)H);
+  const double xs = src[5] - src[4], ys = src[7] - src[6];
+  const double head[ol::kPhaseGridHead] = {
+      src[0], src[1], (double)W, (double)H, src[4], xs, src[6], ys, (double)(W - 1),
+      (double)(H - 1), (double)(W - 1) / xs, (double)(H - 1) / ys, (double)n_scale};
+  out.insert(out.end(), head, head + ol::kPhaseGridHead);
+  int_slots.push_back(base + 2);
+  int_slots.push_back(base + 3);
+  int_slots.push_back(base + 12);
+  out.insert(out.end(), src + 9, src + n);
+  return OL_OK;
+}
+
 // argument validation + every host-side conversion of ol_system_create / ol_system_update
 int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
                  const double* coeffs, int32_t n_coeffs, const ol_surface_optics* optics,
@@ -808,7 +877,8 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     const ol_surface_desc& s = surf[i];
     HostSurf& d = dev[i];
     std::memset(&d, 0, sizeof(d));
-    if (s.geom_kind < OL_GEOM_PLANE || s.geom_kind > OL_GEOM_STANDARD_GRATING)
+    if (s.geom_kind < OL_GEOM_PLANE || s.geom_kind > OL_GEOM_PLANE_PHASE ||
+        s.geom_kind == 13)   // (13: never assigned, refused as it always was)
       return failf(OL_EUNSUPPORTED, "surface %d: geometry kind %d", i, s.geom_kind);
     if (s.interaction < OL_INTERACT_RECORD_ONLY || s.interaction > OL_INTERACT_REFLECT)
       return failf(OL_EUNSUPPORTED, "surface %d: interaction %d", i, s.interaction);
@@ -828,6 +898,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     if (s.geom_kind == OL_GEOM_FORBES_Q2D) d.geom = ol::kGeomForbesQ2d;
     if (s.geom_kind == OL_GEOM_PLANE_GRATING) d.geom = ol::kGeomPlaneGrating;
     if (s.geom_kind == OL_GEOM_STANDARD_GRATING) d.geom = ol::kGeomStandardGrating;
+    if (s.geom_kind == OL_GEOM_PLANE_PHASE) d.geom = ol::kGeomPlanePhase;
     d.interaction = s.interaction;
     d.aperture_kind = s.aperture_kind;
     d.coating_kind = s.coating_kind;
@@ -835,7 +906,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     d.poly_cols = s.poly_cols;
     d.flags = (s.flags & OL_SURF_ROTATED) ? ol::kSurfRotated : 0u;
     const bool inf_r = std::isinf(s.radius) || s.geom_kind == OL_GEOM_PLANE ||
-                       s.geom_kind == OL_GEOM_PLANE_GRATING;
+                       s.geom_kind == OL_GEOM_PLANE_GRATING || s.geom_kind == OL_GEOM_PLANE_PHASE;
     if (inf_r) d.flags |= ol::kSurfRadiusInf;
     if ((s.flags & OL_SURF_REFERENCE_ROOT) && !inf_r &&
         (s.geom_kind == OL_GEOM_STANDARD || s.geom_kind == OL_GEOM_STANDARD_GRATING))
@@ -1050,6 +1121,10 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
       dcoef.push_back(std::sin(src[2]));
       dcoef.push_back(std::cos(src[2]));
       dcoef.push_back(std::tan(src[2]));
+    } else if (ol::is_phase_kind(s.geom_kind)) {
+      // public block (ol_geom_kind, include/optiland_hip.h) -> device block (phase_device.h)
+      if (int rc = stage_phase_block(i, s, src, n_wavelengths, dcoef, int_slots)) return rc;
+      d.n_coeff = s.n_coeff;
     } else {
       d.n_coeff = 0;
     }
@@ -1089,6 +1164,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
                                     surf[i].geom_kind != OL_GEOM_PLANE &&
                                     surf[i].geom_kind != OL_GEOM_STANDARD &&
                                     !ol::is_grating_kind(surf[i].geom_kind) &&
+                                    !ol::is_phase_kind(surf[i].geom_kind) &&
                                     surf[i].interaction != OL_INTERACT_RECORD_ONLY
                                 ? 1 : 0);
   }
@@ -1195,6 +1271,7 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const r
   if (int rc = rule_wavelength("ol_trace", v.n_wl, wavelength_index)) return rc;
   if (int rc = rule_no_forbes("ol_trace", v, first_surface, last_surface)) return rc;
   if (int rc = rule_no_grating("ol_trace", v, first_surface, last_surface)) return rc;
+  if (int rc = rule_no_phase("ol_trace", v, first_surface, last_surface)) return rc;
   if (n_rays == 0) return OL_OK;
   if (int rc = rule_current_device("ol_trace", v)) return rc;
   if (int rc = rule_planes("ol_trace", "rays", rays, 8)) return rc;
@@ -1232,6 +1309,7 @@ int ol_newton_count(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* con
   if (!iterations) return failf(OL_EINVAL, "ol_newton_count: iterations is NULL");
   if (int rc = rule_no_forbes("ol_newton_count", v, first_surface, surface)) return rc;
   if (int rc = rule_no_grating("ol_newton_count", v, first_surface, surface)) return rc;
+  if (int rc = rule_no_phase("ol_newton_count", v, first_surface, surface)) return rc;
   if (!v.ref_newton[surface])
     return failf(OL_EINVAL, "ol_newton_count: surface %d is not a traced Newton-Raphson surface "
                             "with OL_SURF_REFERENCE_NEWTON", surface);

@@ -99,8 +99,15 @@ enum : int {
   // OL_GEOM_PLANE_GRATING (11) / OL_GEOM_STANDARD_GRATING (12), renumbered likewise: traced by
   // grating.hip alone (grating_device.h); block: {order, period, sin a, cos a, tan a}
   kGeomPlaneGrating = 18,
-  kGeomStandardGrating = 19
+  kGeomStandardGrating = 19,
+  // OL_GEOM_PLANE_PHASE (14), renumbered likewise: traced by phase.hip alone (phase_device.h,
+  // which has the layout of the block)
+  kGeomPlanePhase = 20
 };
+// profile kinds of a kGeomPlanePhase block ([0] of it) and the values of a grid block in front of
+// its scales (phase_device.h)
+enum : int { kPhaseConstant = 0, kPhaseLinear = 1, kPhaseRadial = 2, kPhaseGrid = 3 };
+constexpr int kPhaseGridHead = 13;
 enum : int { kRecordOnly = 0, kRefract = 1, kReflect = 2 };
 enum : int {
   kApNone = 0, kApRadial = 1, kApOffsetRadial = 2, kApRect = 3, kApElliptical = 4,

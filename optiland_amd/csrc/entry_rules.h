@@ -113,11 +113,22 @@ inline int rule_no_grating(const char* who, const SystemView& v, int32_t first, 
   return OL_OK;
 }
 
+// phase-profile rows (OL_GEOM_PLANE_PHASE) likewise: ol_trace_phase alone (phase.hip) adds the
+// gradient of the phase, the fused kernels would refract
+inline int rule_no_phase(const char* who, const SystemView& v, int32_t first, int32_t last) {
+  for (int32_t s = first; s <= last; ++s)
+    if (is_phase_kind(v.geom[s]))
+      return failf(OL_EUNSUPPORTED, "%s: surface %d is a phase surface: trace it with "
+                                    "ol_trace_phase and cut the range there", who, s);
+  return OL_OK;
+}
+
 // the fused entry points (one launch: generate -> trace [-> reduce]) walk the whole system and do
 // not serve ranges whose Newton iteration count is a property of the batch
 inline int rule_no_reference_newton(const char* who, const SystemView& v) {
   if (int rc = rule_no_forbes(who, v, 0, v.n_surf - 1)) return rc;
   if (int rc = rule_no_grating(who, v, 0, v.n_surf - 1)) return rc;
+  if (int rc = rule_no_phase(who, v, 0, v.n_surf - 1)) return rc;
   for (int32_t s = 0; s < v.n_surf; ++s)
     if (v.ref_newton[s])
       return failf(OL_EUNSUPPORTED, "%s: the system carries OL_SURF_REFERENCE_NEWTON surfaces "

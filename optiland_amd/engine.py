@@ -456,8 +456,8 @@ def split_trace(forbes, first: int, last: int, rec, rec_first: int, fused, one) 
     """Walk surfaces [first, last] as fused runs and single Forbes launches, in order.
 
     forbes: the table's single-launch rows -- `SystemTable.forbes` and, with them,
-    `SystemTable.gratings`: the caller passes the union and tells the two apart in `one` (the
-    parameter keeps its name: callers pass it by position or by this name).  rec: the caller's
+    `SystemTable.gratings` and `SystemTable.phases`: the caller passes the union and tells them
+    apart in `one` (the parameter keeps its name: callers pass it by position or by this name).  rec: the caller's
     record block or None; its row 0 holds surface `rec_first`.  `fused(a, b, rec_view, rec_from, midrange)` traces
     the run [a, b] -- `rec_view` is the part of the block whose row 0 is surface `rec_from`, or
     None when the run lies in front of the first recorded surface; `one(s, row, midrange)` traces
@@ -809,10 +809,10 @@ class HipSystem:
               defer_status: bool = False, zero_status: bool = True,
               spot=None, record_first: int | None = None,
               nonunit_directions: bool = False, _status_to=None) -> TraceResult:
-        """Launch the fused trace.  A range that holds Forbes rows (`table.forbes`) or grating
-        rows (`table.gratings`) is split into fused runs and one `trace_forbes` / `trace_grating`
-        launch per such row, all writing into the same record block and status word (unpolarised,
-        no spot epilogue).
+        """Launch the fused trace.  A range that holds Forbes rows (`table.forbes`), grating
+        rows (`table.gratings`) or phase rows (`table.phases`) is split into fused runs and one
+        `trace_forbes` / `trace_grating` / `trace_phase` launch per such row, all writing into the
+        same record block and status word (unpolarised, no spot epilogue).
 
         rays: sequence of 8 contiguous 1-D device tensors (x,y,z,L,M,N,i,opd) of one
         dtype -- the initial state.  record: True (allocate), False/None, or a
@@ -857,11 +857,12 @@ class HipSystem:
                 raise ValueError("record must be a contiguous (rows, 8, stride>=n) tensor")
         if write_rays is None:
             write_rays = rec is None
-        singles = self.table.forbes + self.table.gratings
+        singles = self.table.forbes + self.table.gratings + self.table.phases
         if singles and any(first <= f <= last for f in singles):
             if prt is not None or spot is not None:
-                raise ValueError("a range with Forbes surfaces or gratings is traced unpolarised "
-                                 "and without the spot epilogue (cut it at those surfaces)")
+                raise ValueError("a range with Forbes surfaces, gratings or phase surfaces is "
+                                 "traced unpolarised and without the spot epilogue (cut it at "
+                                 "those surfaces)")
             return self._trace_split(rays, int(wavelength_index), rec, rec_first, int(first),
                                      int(last), write_rays, check_status, defer_status,
                                      zero_status)
@@ -966,9 +967,30 @@ class HipSystem:
                                   record_row, write_rays, midrange, check_status, defer_status,
                                   zero_status)
 
+    # ---- phase-profile planes (ol_trace_phase: one surface, one launch) ------------------------
+    def can_trace_phase(self) -> bool:
+        return _capi.has_trace_phase(self.lib)
+
+    def trace_phase(self, rays, surface: int, wavelength_index: int = 0, record_row=None,
+                    write_rays: bool | None = None, midrange: bool = False,
+                    check_status: bool = True, defer_status: bool = False,
+                    zero_status: bool = True) -> int:
+        """`trace_grating` for the ONE phase row `surface` of the table (`ol_trace_phase`): frame
+        change, plane hit, the gradient of the phase profile added to the tangential wave vector
+        at the wavelength `table.wavelengths[wavelength_index]`, the phase taken off the optical
+        path, back to the global frame.  An evanescent ray leaves intensity 0, a finite direction
+        and no status bit, as in the reference.  A missing kernel is an error."""
+        if not self.can_trace_phase():
+            raise _capi.HipExtensionError("the loaded library has no ol_trace_phase: rebuild it")
+        wl = float(self.table.wavelengths[int(wavelength_index)])
+        return self._trace_single("ol_trace_phase", (wl,), self.table.phases, "a phase", rays,
+                                  surface, wavelength_index,
+                                  record_row, write_rays, midrange, check_status, defer_status,
+                                  zero_status)
+
     def _trace_single(self, entry, extra, rows, kind, rays, surface, wavelength_index, record_row,
                       write_rays, midrange, check_status, defer_status, zero_status) -> int:
-        """The launch `trace_forbes` and `trace_grating` share: `entry` takes `extra` behind the
+        """The launch `trace_forbes`, `trace_grating` and `trace_phase` share: `entry` takes `extra` behind the
         wavelength index and serves the table's `rows` ("`kind` row"), everything else alike --
         the checks in the order `trace_forbes` always made them."""
         rays = list(rays)
@@ -1009,7 +1031,7 @@ class HipSystem:
 
     def _trace_split(self, rays, wl, rec, rec_first, first, last, write_rays, check_status,
                      defer_status, zero_status) -> TraceResult:
-        """`trace` over a range with Forbes or grating rows (`split_trace`).  The state travels in
+        """`trace` over a range with Forbes, grating or phase rows (`split_trace`).  The state travels in
         `rays` themselves (write_rays) or in a private copy of them; every launch ORs into the one
         status word, except that what a fused run in FRONT of a later launch reports about its
         own last surface (STATUS_NAN_DIRECTION) is dropped: it is not the end of this trace."""
@@ -1030,15 +1052,16 @@ class HipSystem:
                        zero_status=False, record_first=r0 if (r0 is not None and r0 != a) else None,
                        _status_to=word)
 
-        gratings = set(self.table.gratings)
+        gratings, phases = set(self.table.gratings), set(self.table.phases)
 
         def one(s, row, midrange):
-            launch = self.trace_grating if s in gratings else self.trace_forbes
+            launch = self.trace_grating if s in gratings else \
+                self.trace_phase if s in phases else self.trace_forbes
             launch(work, s, wl, record_row=row, write_rays=True, midrange=midrange,
                    check_status=check_status, defer_status=True, zero_status=False)
 
-        split_trace(self.table.forbes + self.table.gratings, first, last, rec, rec_first, fused,
-                    one)
+        split_trace(self.table.forbes + self.table.gratings + self.table.phases, first, last, rec,
+                    rec_first, fused, one)
         if mid:
             self._status.bitwise_or_(mid[0].bitwise_and_(~S.STATUS_NAN_DIRECTION))
         status = int(self._status.item()) if (check_status and not defer_status) else 0

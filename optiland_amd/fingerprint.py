@@ -237,10 +237,32 @@ def _forbes_terms(geom, keep):
     return out
 
 
+def _phase_terms(im, keep, memo=None):
+    """The phase profile of a PhaseInteractionModel (optiland/phase/), None for every other
+    interaction model.  The one-level walk of `im.__dict__` sees the profile by identity only, and
+    what the packer reads lies one level below: the radial coefficient LIST item by item; period,
+    angle, order, efficiency and the prepared K_x / K_y of the linear grating; the constant phase;
+    the coordinate and node arrays of the gridded profiles (tensors by identity and `_version`,
+    arrays by content); the height profile's material, one level deep like the surface's own.  An
+    edit in place of any of them re-packs."""
+    p = getattr(im, "phase_profile", None)
+    d = getattr(p, "__dict__", None)
+    if d is None:
+        return None
+    keep.append(p)
+    m = d.get("material")
+    return ("phase", type(p).__name__, id(p),
+            tuple([(k, _tok(v, keep)) for k, v in d.items()]),
+            _material(m, keep, {} if memo is None else memo) if hasattr(m, "__dict__") else None)
+
+
 def _surface_token_py(s, keep, memo):
     geom = s.geometry
     im = getattr(s, "interaction_model", None)
     terms = _forbes_terms(geom, keep)
+    phase = _phase_terms(im, keep, memo)
+    if phase is not None:
+        terms = (phase,) if terms is None else terms + (phase,)
     return (
         type(s).__name__, id(s),
         _obj(geom, keep, memo), _cs(getattr(geom, "cs", None), keep, memo),
@@ -257,6 +279,9 @@ def _surface_token_py(s, keep, memo):
 def _surface_token_native(s, keep, memo):
     tok = _NATIVE.surface_token(s, keep, memo, _SURFACE_SKIP)
     terms = _forbes_terms(s.geometry, keep)
+    phase = _phase_terms(getattr(s, "interaction_model", None), keep, memo)
+    if phase is not None:
+        terms = (phase,) if terms is None else terms + (phase,)
     return tok if terms is None else tuple(tok) + (terms,)
 
 

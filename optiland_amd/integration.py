@@ -958,7 +958,9 @@ def _make_tracer_class():
 # --------------------------------------------------------------------------------------
 _SG = {"device": None, "force": False, "count": 0, "fallbacks": 0, "foreign": 0,
        # enable(gratings=...): diffraction gratings as device work (OPTILAND_HIP_GRATINGS=0: off)
-       "gratings": os.environ.get("OPTILAND_HIP_GRATINGS", "1") != "0"}
+       "gratings": os.environ.get("OPTILAND_HIP_GRATINGS", "1") != "0",
+       # enable(phases=...): phase-profile planes likewise (OPTILAND_HIP_PHASES=0: off)
+       "phases": os.environ.get("OPTILAND_HIP_PHASES", "1") != "0"}
 # settings of the class-wide patch (enable())
 _ENABLE = {"device": None, "force": False, "lazy": False}
 _PLANE_ATTRS = ("x", "y", "z", "L", "M", "N", "i", "opd")
@@ -1006,24 +1008,27 @@ def _sg_table(group, wavelength):
     declares that its engines trace them (`tracer._make_engine.traces_gratings`) and
     `enable(gratings=False)` / OPTILAND_HIP_GRATINGS=0 has not switched them off: decided HERE,
     before packing, so that the production path packs once and a stand-in factory that knows
-    nothing of gratings gets the table -- and the reference's own surface -- it always got."""
+    nothing of gratings gets the table -- and the reference's own surface -- it always got.
+    Phase-profile planes (`table.phases`) likewise: `traces_phases`, `enable(phases=False)` /
+    OPTILAND_HIP_PHASES=0."""
     gratings = bool(_SG["gratings"]) and bool(getattr(_tracer._make_engine, "traces_gratings",
                                                       False))
+    phases = bool(_SG["phases"]) and bool(getattr(_tracer._make_engine, "traces_phases", False))
     tok = None
     if _fp.ENABLED:
         tok, _keep = _fp.surfaces_token(group.surfaces, wavelength)
         memo = group.__dict__.get("_hip_sg_memo")
         memo = memo.value if memo is not None else None
-        if memo is not None and memo[0] == tok and memo[3] == gratings:
+        if memo is not None and memo[0] == tok and memo[3] == (gratings, phases):
             return memo[2]
     try:
         table = pack_surfaces(group.surfaces, [wavelength], name="SurfaceGroup", tolerate=True,
-                              gratings=gratings)
+                              gratings=gratings, phases=phases)
     except UnsupportedSystem:
         table = None
     if tok is not None:
         tok, keep = _fp.surfaces_token(group.surfaces, wavelength)  # after the pack
-        group.__dict__["_hip_sg_memo"] = _Volatile((tok, keep, table, gratings))
+        group.__dict__["_hip_sg_memo"] = _Volatile((tok, keep, table, (gratings, phases)))
     return table
 
 
@@ -1116,7 +1121,7 @@ def _hip_surface_group_trace(group, rays, skip):
     (interactions/refractive_reflective_model.py:41) and PolarizedRays.p is advanced
     from its CURRENT value (rays/polarized_rays.py:180-202).
 
-    Surfaces the fused path does not implement (thin lens, phase, NURBS
+    Surfaces the fused path does not implement (thin lens, NURBS
     / grid-sag geometry, GRIN media, BSDF, thin-film coating ...) do not disqualify the
     whole system: they are traced by their own `Surface.trace(rays)` on the same device
     tensors, and the runs of supported surfaces between them are one launch each
@@ -1135,7 +1140,13 @@ def _hip_surface_group_trace(group, rays, skip):
     DiffractiveInteractionModel) are the same: one `ol_trace_grating` launch inside a run, served,
     a polarised bundle excepted.  They are in the table only when the engine that will trace it
     can trace them and `enable(gratings=False)` has not switched them off (`_sg_table`);
-    otherwise the surface is in `table.unsupported` and the reference's own, as before."""
+    otherwise the surface is in `table.unsupported` and the reference's own, as before.
+
+    Phase-profile planes (`table.phases`: a Plane with PhaseInteractionModel and one of the five
+    profiles of optiland/phase/) are the same again: one `ol_trace_phase` launch inside a run,
+    served, a polarised bundle excepted; packed as such only for an engine that traces them and
+    while `enable(phases=False)` has not switched them off.  The gridded profiles reproduce the
+    TORCH backend's bilinear interpolant, whatever backend is active."""
     import optiland.backend as be
     from optiland.rays import PolarizedRays as RefPolarizedRays
     from optiland.rays import RealRays as RefRealRays
@@ -1159,7 +1170,7 @@ def _hip_surface_group_trace(group, rays, skip):
         return None
     foreign = set(table.unsupported)
     if polarized:
-        foreign |= set(table.forbes) | set(table.gratings)
+        foreign |= set(table.forbes) | set(table.gratings) | set(table.phases)
     if len(foreign) >= n_s - skip - (1 if skip == 0 else 0):
         return None  # nothing but the object row would run fused
     if table.uses_polarization and not polarized:
@@ -1331,7 +1342,7 @@ def _set_reference_newton(reference_newton):
 
 
 def enable(device=None, force=False, analyses=True, lazy_records=False, placed_records=None,
-           reference_root=None, reference_newton=None, gratings=None):
+           reference_root=None, reference_newton=None, gratings=None, phases=None):
     """Route EVERY `Optic` (existing and future) through the HIP path.
 
     Patches `RealRayTracer.trace / trace_generic` (raytrace/real_ray_tracer.py:58-154)
@@ -1389,12 +1400,18 @@ def enable(device=None, force=False, analyses=True, lazy_records=False, placed_r
     gratings (surface type "grating") are one `ol_trace_grating` launch between two fused runs.
     False: they are traced by the reference's own `Surface.trace`, as every surface the fused
     path does not know.
+
+    `phases` (default on; None = leave as is, OPTILAND_HIP_PHASES=0 seeds it off): a plane with a
+    phase profile (PhaseInteractionModel: metalens, diffractive or holographic element) is one
+    `ol_trace_phase` launch between two fused runs.  False: the reference's own `Surface.trace`.
     """
     _set_record_pool(placed_records)
     _set_reference_root(reference_root)
     _set_reference_newton(reference_newton)
     if gratings is not None:
         _SG["gratings"] = bool(gratings)
+    if phases is not None:
+        _SG["phases"] = bool(phases)
     cls = _make_tracer_class()
     from optiland.raytrace.real_ray_tracer import RealRayTracer
 

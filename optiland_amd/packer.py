@@ -273,6 +273,90 @@ def _pack_grating(geom, row, coeffs: list) -> None:
     coeffs.extend([order, period, angle])
 
 
+def _phase_classes():
+    """(Plane, PhaseInteractionModel, (RadialPhaseProfile, LinearGratingPhaseProfile,
+    ConstantPhaseProfile, GridPhaseProfile, HeightProfile)) of the reference, or None where it has
+    no phase model."""
+    try:
+        from optiland.geometries.plane import Plane
+        from optiland.interactions.phase_interaction_model import PhaseInteractionModel
+        from optiland.phase.constant import ConstantPhaseProfile
+        from optiland.phase.grid import GridPhaseProfile
+        from optiland.phase.height_profile import HeightProfile
+        from optiland.phase.linear_grating import LinearGratingPhaseProfile
+        from optiland.phase.radial import RadialPhaseProfile
+    except Exception:  # noqa: BLE001 - a reference without the phase model
+        return None
+    return Plane, PhaseInteractionModel, (RadialPhaseProfile, LinearGratingPhaseProfile,
+                                          ConstantPhaseProfile, GridPhaseProfile, HeightProfile)
+
+
+def _is_phase(surf) -> bool:
+    """A Plane WITH the phase interaction model (the reference documents the model for planes
+    only; on any other geometry the surface stays the reference's)."""
+    classes = _phase_classes()
+    return classes is not None and isinstance(surf.geometry, classes[0]) \
+        and isinstance(surf.interaction_model, classes[1])
+
+
+def _grid64(v) -> np.ndarray:
+    """A backend array as float64 NumPy."""
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    return np.asarray(v, dtype=np.float64)
+
+
+def _pack_phase(surf, wl, row, coeffs: list) -> None:
+    """A phase-profile plane in full (tolerate mode only): the self-describing block of
+    OL_GEOM_PLANE_PHASE (include/optiland_hip.h).  Raises `UnsupportedSystem` for what stays with
+    the reference's own surface: a profile whose class is not EXACTLY one of the five (a subclass
+    may compute anything), a grid with fewer than 2 nodes on an axis, with coincident end points
+    or a shape that does not match its coordinates, a height profile whose material has no
+    `n()`, parameters that are not finite."""
+    radial, linear, constant, grid, height = _phase_classes()[2]
+    profile = surf.interaction_model.phase_profile
+    cls = type(profile)
+    try:
+        eff = _f(profile.efficiency)
+        if cls is constant:
+            block = [float(S.PHASE_CONSTANT), eff, _f(profile.phase)]
+        elif cls is linear:
+            # what the reference's get_phase / get_gradient use: order * 2 pi / period *
+            # (cos, sin)(angle), formed when the profile was built
+            block = [float(S.PHASE_LINEAR), eff, _f(profile._K_x), _f(profile._K_y)]
+        elif cls is radial:
+            terms = [_f(c) for c in profile.coefficients]
+            block = [float(S.PHASE_RADIAL), eff, float(len(terms))] + terms
+        elif cls is grid or cls is height:
+            xs, ys = _grid64(profile.x_coords).reshape(-1), _grid64(profile.y_coords).reshape(-1)
+            nodes = _grid64(profile.phase_grid if cls is grid else profile.height_map)
+            if xs.size < 2 or ys.size < 2 or nodes.shape != (ys.size, xs.size):
+                raise UnsupportedSystem(f"phase grid of shape {nodes.shape} on {ys.size} x "
+                                        f"{xs.size} coordinates")
+            if xs[0] == xs[-1] or ys[0] == ys[-1]:
+                raise UnsupportedSystem("phase grid with coincident end points")
+            scales = []
+            if cls is height:
+                if not callable(getattr(profile.material, "n", None)):
+                    raise UnsupportedSystem("height profile whose material has no n()")
+                scales = [2.0 * math.pi / (float(w) * 1e-3)
+                          * (_scalar_index(profile.material, float(w), "n") - 1.0) for w in wl]
+            block = [float(S.PHASE_GRID), eff, float(xs.size), float(ys.size), float(xs[0]),
+                     float(xs[-1]), float(ys[0]), float(ys[-1]), float(len(scales))] + scales \
+                + nodes.reshape(-1).tolist()
+        else:
+            raise UnsupportedSystem(f"phase profile {cls.__name__} is not on the device")
+    except UnsupportedSystem:
+        raise
+    except Exception as exc:  # noqa: BLE001 - a profile the packer cannot read is the reference's
+        raise UnsupportedSystem(f"phase profile {cls.__name__}: {exc}") from exc
+    if not all(math.isfinite(v) for v in block):
+        raise UnsupportedSystem(f"phase profile {cls.__name__} with parameters that are not finite")
+    row["geom_kind"] = S.GEOM_PLANE_PHASE
+    row["n_coeff"] = len(block)
+    coeffs.extend(block)
+
+
 def _pack_geometry(geom, row, coeffs: list, forbes: bool = False, grating: bool = False):
     name = type(geom).__name__
     row["coeff_offset"] = len(coeffs)
@@ -503,12 +587,17 @@ def _is_grating_row(row) -> bool:
     return int(row["geom_kind"]) in (S.GEOM_PLANE_GRATING, S.GEOM_STANDARD_GRATING)
 
 
-def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, gratings: bool = False):
+def _is_phase_row(row) -> bool:
+    return int(row["geom_kind"]) == S.GEOM_PLANE_PHASE
+
+
+def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, gratings: bool = False,
+                        phases: bool = False):
     """One surface, packed by itself: (desc row, its coefficient block as a list with every
     offset RELATIVE to the block, optics rows per wavelength).  Raises `UnsupportedSystem`.
     forbes: a Forbes surface is packed as a row of its own kind (`pack_surfaces(tolerate=True)`)
     instead of raising; gratings: so is a diffraction grating (`pack_surfaces(tolerate=True,
-    gratings=True)`)."""
+    gratings=True)`); phases: and so is a phase-profile plane (`phases=True`)."""
     row = np.zeros((), dtype=S.SURFACE_DESC_DTYPE)
     opt = np.zeros(wl.size, dtype=S.SURFACE_OPTICS_DTYPE)
     coeffs: list = []
@@ -521,15 +610,19 @@ def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, grating
         row["flags"] |= S.SURF_REFERENCE_ROOT
     im = surf.interaction_model
     grating = gratings and not is_object and _is_grating(surf)
-    if type(im).__name__ != "RefractiveReflectiveModel" and not grating:
+    phase = phases and not is_object and _is_phase(surf)
+    if type(im).__name__ != "RefractiveReflectiveModel" and not grating and not phase:
         raise UnsupportedSystem(
             f"interaction model {type(im).__name__} is not on the fused path"
         )
     if getattr(im, "bsdf", None) is not None:
         raise UnsupportedSystem("BSDF scatter is not on the fused path")
     _pack_geometry(geom, row, coeffs, forbes and not is_object, grating)
+    if phase:   # (the geometry is a Plane: `_is_phase`)
+        _pack_phase(surf, wl, row, coeffs)
     if S.OPTIONS["reference_newton"] and int(row["geom_kind"]) not in (S.GEOM_PLANE,
-                                                                      S.GEOM_STANDARD):
+                                                                      S.GEOM_STANDARD,
+                                                                      S.GEOM_PLANE_PHASE):
         # the reference's batch-global stop rule on this Newton-Raphson surface (opt-in)
         row["flags"] |= S.SURF_REFERENCE_NEWTON
     _pack_aperture(surf.aperture, row, coeffs)
@@ -538,6 +631,8 @@ def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, grating
         raise UnsupportedSystem("polarisation-dependent coating on a Forbes surface")
     if grating and int(row["coating_kind"]) >= S.COAT_FRESNEL:
         raise UnsupportedSystem("polarisation-dependent coating on a grating")
+    if phase and int(row["coating_kind"]) >= S.COAT_FRESNEL:
+        raise UnsupportedSystem("polarisation-dependent coating on a phase surface")
     if is_object:
         # ObjectSurface.trace only records (surfaces/object_surface.py:56-93)
         row["interaction"] = S.INTERACT_RECORD_ONLY
@@ -599,7 +694,7 @@ def _relocate(row, local: list, base: int):
 
 def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
                   tolerate: bool = False, tokens=None, cache: dict | None = None,
-                  keep=None, gratings: bool = False) -> SystemTable:
+                  keep=None, gratings: bool = False, phases: bool = False) -> SystemTable:
     """Flatten a sequence of reference `Surface` objects (a `SurfaceGroup`'s list) for
     the given wavelengths (microns): everything `SurfaceGroup.trace`
     (surfaces/surface_group.py:245-257) needs -- no ray-generator scalars, no
@@ -618,7 +713,11 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
     grating (PlaneGrating / StandardGratingGeometry with DiffractiveInteractionModel, by
     `isinstance`) is packed likewise and listed in `table.gratings`; without `gratings` it stays
     in `table.unsupported`, and so does one the kernel does not serve (`_pack_grating`, a BSDF, a
-    Jones coating, an inhomogeneous medium).
+    Jones coating, an inhomogeneous medium).  `phases` does the same for a Plane with
+    PhaseInteractionModel (`_is_phase`; `HipSystem.can_trace_phase`): packed and listed in
+    `table.phases` with `tolerate` AND `phases`, in `table.unsupported` without, and also when
+    the kernel does not serve it (`_pack_phase`, a BSDF, a Jones coating, an inhomogeneous
+    medium).
 
     `tokens` + `cache` (both or neither): per-surface change-detector tokens
     (fingerprint.surface_token, i.e. element [1] of `optic_token`) and a dict the caller
@@ -674,10 +773,15 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
                     if not tolerate:
                         raise UnsupportedSystem("a grating is not on the fused path")
                     packed = None   # (cached by a pack that served gratings: decided below)
+                if packed is not None and _is_phase_row(packed[0]) and not (tolerate and phases):
+                    if not tolerate:
+                        raise UnsupportedSystem("a phase surface is not on the fused path")
+                    packed = None   # (cached by a pack that served phase surfaces)
         if packed is None:
             try:
                 packed = _pack_surface_local(i == 0, surf, wl, forbes=tolerate,
-                                             gratings=tolerate and gratings)
+                                             gratings=tolerate and gratings,
+                                             phases=tolerate and phases)
             except UnsupportedSystem:
                 if not tolerate or i == 0:
                     raise
@@ -706,7 +810,8 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
     )
     table.last_thickness = _f(surfaces[-1].thickness) if n_s else 0.0
     table.unsupported = tuple(unsupported)
-    if use_cache and not unsupported and not table.forbes and not table.gratings:
+    if use_cache and not unsupported and not table.forbes and not table.gratings \
+            and not table.phases:
         cache["assembled"] = (tuple(id(s_) for s_ in surfaces), wl_key, list(tokens), bases,
                               table)
     return table

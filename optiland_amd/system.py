@@ -29,6 +29,10 @@ GEOM_CHEBYSHEV, GEOM_BICONIC, GEOM_TOROIDAL = 6, 7, 8
 GEOM_FORBES_Q, GEOM_FORBES_Q2D = 9, 10
 # diffraction gratings likewise (ol_trace_grating); block: {order, period (um), groove angle}
 GEOM_PLANE_GRATING, GEOM_STANDARD_GRATING = 11, 12
+# a plane with a phase profile likewise (ol_trace_phase); its block describes itself: the comment
+# of ol_geom_kind in include/optiland_hip.h has the layout
+GEOM_PLANE_PHASE = 14   # (13 is no kind: the library refuses it as unknown, as it always did)
+PHASE_CONSTANT, PHASE_LINEAR, PHASE_RADIAL, PHASE_GRID = 0, 1, 2, 3
 INTERACT_RECORD_ONLY, INTERACT_REFRACT, INTERACT_REFLECT = 0, 1, 2
 AP_NONE, AP_RADIAL, AP_OFFSET_RADIAL, AP_RECTANGULAR, AP_ELLIPTICAL = 0, 1, 2, 3, 4
 AP_COMPOSITE = 5
@@ -75,6 +79,7 @@ GEOM_NAMES = {
     GEOM_FORBES_Q2D: "forbes_q2d",
     GEOM_PLANE_GRATING: "plane_grating",
     GEOM_STANDARD_GRATING: "standard_grating",
+    GEOM_PLANE_PHASE: "plane_phase",
 }
 
 # numpy image of `ol_surface_desc`; align=True reproduces the C layout.
@@ -212,6 +217,17 @@ class SystemTable:
                                            | (g == GEOM_STANDARD_GRATING))[0])
         return memo
 
+    @property
+    def phases(self) -> tuple:
+        """Indices of the phase-profile rows (GEOM_PLANE_PHASE): each is one `ol_trace_phase`
+        launch between two fused runs, like the grating rows."""
+        memo = self.__dict__.get("_phases")
+        if memo is None:
+            g = self.surfaces["geom_kind"]
+            memo = self.__dict__["_phases"] = tuple(
+                int(i) for i in np.nonzero(g == GEOM_PLANE_PHASE)[0])
+        return memo
+
     def reference_newton_surfaces(self, first: int = 0, last: int | None = None) -> list:
         """Traced Newton-Raphson surfaces of [first, last] that carry SURF_REFERENCE_NEWTON (the
         reference's batch-global stop rule, newton_raphson.py:137-166): their iteration count is
@@ -225,6 +241,7 @@ class SystemTable:
                                            & (s["geom_kind"] != GEOM_STANDARD)
                                            & (s["geom_kind"] != GEOM_PLANE_GRATING)
                                            & (s["geom_kind"] != GEOM_STANDARD_GRATING)
+                                           & (s["geom_kind"] != GEOM_PLANE_PHASE)
                                            & (s["interaction"] != INTERACT_RECORD_ONLY))[0]]
         if not memo:
             return memo

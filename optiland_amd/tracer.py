@@ -41,6 +41,8 @@ def _make_engine(table: SystemTable, device):
 # (`pack_surfaces(gratings=True)`); a replacement that says nothing gets the table without them
 # and the reference's own surface there.
 _make_engine.traces_gratings = True
+# ... and likewise for phase-profile planes (`pack_surfaces(phases=True)`, `table.phases`)
+_make_engine.traces_phases = True
 
 
 class RecordedSurfaces:

@@ -1,0 +1,396 @@
+"""What the phase-surface tests share (tests/test_phase_cpu.py, tests/test_gpu_phase.py) and what
+tools/make_golden_phase.py builds its fixture from: singlet-like optics (object, stop, the phase
+plane, image) with the five profiles of the reference's optiland/phase/, the fixture
+tests/golden/phase.npz, the bounds, the case files of tests/hostphase and the CPU stand-in engine
+of the drop-in test.
+
+Bounds: those of tests/_grating.py (`compare`, `bounds`, `scale_of` are its functions) -- the
+contract 1e-6 (fp64) / 1e-4 (fp32), and fp64 within 1e-12, positions and path lengths relative to
+the system scale.  The fixture holds no ray at either of two discontinuities:
+  * |S| / n2'^2 < 1e-2 (S = n2'^2 - tx^2 - ty^2, the radicand of the interaction): the clip mask
+    would depend on rounding and d k / d S ~ 1 / sqrt(S);
+  * within 1e-4 of a cell pitch of a grid line of a gridded profile: the gradient of the bilinear
+    interpolant jumps there, and fp32 rounding of the grid coordinate is a few 1e-6 of a pitch.
+The generator drops such rays; `radicand` and `grid_line_distance` below recompute both from the
+table and the recorded rows, in NumPy and from the reference's definitions, and the tests assert
+the margins on the fixture.
+"""
+
+from __future__ import annotations
+
+import functools
+import importlib.util
+import math
+import os
+
+import numpy as np
+
+from optiland_amd import system as S
+from optiland_amd.system import SystemTable
+from tests._grating import (CONTRACT, TIGHT, bounds, compare, pupil_points,  # noqa: F401
+                            run_host, sanitizers_available, scale_of)
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLD = os.path.join(HERE, "golden", "phase.npz")
+MAGIC = int.from_bytes(b"olPHAS", "little")
+
+WAVELENGTHS = (0.587, 0.486)       # the primary one, and the second one of the height cases
+WAVELENGTH = WAVELENGTHS[0]
+MARGIN = 1e-2                      # |S| / n2'^2 of every fixture ray is at least this
+GRID_MARGIN = 1e-4                 # ... and its distance to a grid line, in cell pitches
+GRID_DROP_CAP = 0.01               # at most this share of a case's rays may go at grid lines
+BIG_SET = "disc1027"
+BIG_CASES = ("radial_t", "grid")
+PHASE = 2                          # the phase row of every case: object, stop, phase plane, image
+
+# a metalens of f ~ 47 mm at 0.587 um: a_2 = -k0 / (2 f) ~ -114 rad / mm^2, and two higher terms
+RADIAL = (-114.0, 0.35, -0.004)
+GRID_X = (-2.6, 2.4, 24)           # xmin, xmax, W: the 3 mm beam leaves the grid on every side,
+GRID_Y = (-2.2, 2.5, 18)           # by up to three cells; no node line through the axis
+
+# name -> (profile, keyword edits of the optic / the phase surface, (Hx, Hy), wavelength index)
+CASES = {
+    "radial_t": ("radial", dict(material="N-BK7"), (0.0, 1.0), 0),
+    "radial_r": ("radial", dict(material="mirror"), (0.0, 1.0), 0),
+    "radial_air": ("radial", {}, (1.0, 0.0), 0),
+    "linear_m1": ("linear", dict(order=-1), (0.0, 1.0), 0),
+    "linear_p1": ("linear", dict(order=1), (0.0, 0.0), 0),
+    "constant": ("constant", dict(material="N-BK7"), (0.0, 1.0), 0),
+    "tilted": ("radial", dict(material="N-BK7", rx=0.03, dy=0.4), (1.0, 0.0), 0),
+    "clipped": ("radial", dict(material="N-BK7", aperture=2.5), (0.0, 1.0), 0),
+    "coated_t": ("radial", dict(material="N-BK7", coating=(0.9, 0.05)), (0.0, 0.0), 0),
+    "coated_r": ("radial", dict(material="mirror", coating=(0.9, 0.05)), (0.0, 1.0), 0),
+    # a period near the wavelength, a finite object so that the direction varies over the pupil,
+    # the field at the edge: part of the bundle is evanescent behind the surface
+    "tir_p1": ("linear", dict(order=1, period=0.62e-3, angle=math.pi / 2, efficiency=1.0,
+                              object_distance=20.0), (0.0, -1.0), 0),
+    "tir_m1": ("linear", dict(order=-1, period=0.62e-3, angle=math.pi / 2, efficiency=1.0,
+                              object_distance=20.0, material="mirror"), (0.0, 1.0), 0),
+    "grid": ("grid", dict(material="N-BK7"), (0.0, 1.0), 0),
+    "height": ("height", {}, (0.0, 1.0), 0),
+    "height_blue": ("height", {}, (1.0, 0.0), 1),
+}
+TORCH_CASES = ("grid", "height", "height_blue")   # traced on the reference's torch backend
+TIR_CASES = ("tir_p1", "tir_m1")
+
+
+# ------------------------------------------------------------------ the optics (need the reference)
+def radial_phase(x, y):
+    r2 = np.asarray(x) ** 2 + np.asarray(y) ** 2
+    return sum(a * r2 ** (p + 1) for p, a in enumerate(RADIAL))
+
+
+def grid_axes():
+    return np.linspace(*GRID_X), np.linspace(*GRID_Y)
+
+
+def profile(kind: str, **edit):
+    """One of the reference's five profiles, built on the ACTIVE backend."""
+    import optiland.backend as be
+    from optiland.materials import Material
+    from optiland.phase.constant import ConstantPhaseProfile
+    from optiland.phase.grid import GridPhaseProfile
+    from optiland.phase.height_profile import HeightProfile
+    from optiland.phase.linear_grating import LinearGratingPhaseProfile
+    from optiland.phase.radial import RadialPhaseProfile
+
+    if kind == "radial":
+        return RadialPhaseProfile(coefficients=list(edit.get("coefficients", RADIAL)))
+    if kind == "linear":
+        return LinearGratingPhaseProfile(period=edit.get("period", 5.0e-3),
+                                         angle=edit.get("angle", 0.6),
+                                         order=edit.get("order", 1),
+                                         efficiency=edit.get("efficiency", 0.8))
+    if kind == "constant":
+        return ConstantPhaseProfile(phase=edit.get("phase", 1.3))
+    xs, ys = grid_axes()
+    nodes = radial_phase(xs[None, :], ys[:, None])
+    if kind == "grid":
+        return GridPhaseProfile(be.array(xs), be.array(ys), be.array(nodes))
+    assert kind == "height", kind
+    glass = Material("N-BK7")
+    # the height map that gives the radial lens' phase at the primary wavelength
+    k0 = 2.0 * math.pi / (WAVELENGTH * 1e-3)
+    n0 = float(np.asarray(be.to_numpy(glass.n(WAVELENGTH))).reshape(-1)[0])
+    return HeightProfile(be.array(xs), be.array(ys), be.array(nodes / (k0 * (n0 - 1.0))), glass)
+
+
+def lens(kind: str, **edit):
+    """Object, stop, the phase plane, image.  Keyword edits: `material` behind the plane ("mirror":
+    reflecting), `rx` / `dy`, `aperture` (r_max of a RadialAperture), `coating` (transmittance,
+    reflectance of a SimpleCoating), `object_distance`, everything else goes to `profile`."""
+    import optiland.backend as be
+    from optiland.coatings import SimpleCoating
+    from optiland.optic import Optic
+    from optiland.physical_apertures import RadialAperture
+
+    edit = dict(edit)
+    kw = dict(index=2, radius=be.inf, thickness=40.0)
+    material = edit.pop("material", None)
+    if material is not None:
+        kw["material"] = material
+    if material == "mirror":
+        kw["thickness"] = -40.0
+    for k in ("rx", "dy"):
+        if k in edit:
+            kw[k] = edit.pop(k)
+    if "aperture" in edit:
+        kw["aperture"] = RadialAperture(r_max=edit.pop("aperture"))
+    if "coating" in edit:
+        kw["coating"] = SimpleCoating(*edit.pop("coating"))
+    distance = edit.pop("object_distance", None)
+    out = Optic(name=f"phase_{kind}")
+    out.surfaces.add(index=0, radius=be.inf, thickness=be.inf if distance is None else distance)
+    out.surfaces.add(index=1, radius=be.inf, thickness=5.0, is_stop=True)
+    out.surfaces.add(phase_profile=profile(kind, **edit), **kw)
+    out.surfaces.add(index=3)
+    out.set_aperture(aperture_type="EPD", value=6.0)
+    if distance is None:
+        out.fields.set_type(field_type="angle")
+        out.fields.add(y=0)
+        out.fields.add(y=5)
+        out.fields.add(y=0, x=5)
+    else:
+        out.fields.set_type(field_type="object_height")
+        out.fields.add(y=0)
+        out.fields.add(y=1.5)
+    out.wavelengths.add(value=WAVELENGTHS[0], is_primary=True)
+    if kind == "height":
+        out.wavelengths.add(value=WAVELENGTHS[1])
+    return out
+
+
+def case_lens(name: str):
+    kind, edit, _field, _wl = CASES[name]
+    return lens(kind, **dict(edit))
+
+
+def case_wavelengths(name: str):
+    return list(WAVELENGTHS) if CASES[name][0] == "height" else [WAVELENGTH]
+
+
+def packed(optic, wavelengths=(WAVELENGTH,)) -> SystemTable:
+    """The tolerant pack the drop-in's bridge makes of the optic's surfaces for an engine that
+    traces phase surfaces."""
+    from optiland_amd.packer import pack_surfaces
+
+    return pack_surfaces(optic.surfaces.surfaces, list(wavelengths), name=optic.name,
+                         tolerate=True, phases=True)
+
+
+# ------------------------------------------------------------------ the profiles in NumPy
+def block_of(table: SystemTable, g: int) -> np.ndarray:
+    off, n = int(table.surfaces["coeff_offset"][g]), int(table.surfaces["n_coeff"][g])
+    return np.asarray(table.coeffs[off:off + n], dtype=np.float64)
+
+
+def _grid_fields(block):
+    W, H, n_scale = int(block[2]), int(block[3]), int(block[8])
+    nodes = block[9 + n_scale:9 + n_scale + W * H].reshape(H, W)
+    return W, H, n_scale, nodes
+
+
+def grid_coordinates(block, x, y):
+    """(ix, iy) of the grid row: the reference's normalisation and grid_sample's un-normalisation
+    with align_corners=True, in their order of operations."""
+    W, H = int(block[2]), int(block[3])
+    ix = ((2 * (x - block[4]) / (block[5] - block[4]) - 1) + 1) / 2 * (W - 1)
+    iy = ((2 * (y - block[6]) / (block[7] - block[6]) - 1) + 1) / 2 * (H - 1)
+    return ix, iy
+
+
+def grid_line_distance(block, x, y) -> np.ndarray:
+    """Distance of (x, y) to the nearest grid line on either axis, in cell pitches; inf for a
+    profile without a grid."""
+    if int(block[0]) != S.PHASE_GRID:
+        return np.full(np.shape(x), np.inf)
+    ix, iy = grid_coordinates(block, x, y)
+    return np.minimum(np.abs(ix - np.round(ix)), np.abs(iy - np.round(iy)))
+
+
+def profile_numpy(block, wl_index: int, x, y):
+    """(phi, d phi / dx, d phi / dy) of the row's profile, written from the reference's
+    definitions (phase/*.py; the torch backend's grid_sample with zero padding for the grids),
+    not from the kernel."""
+    kind = int(block[0])
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if kind == S.PHASE_CONSTANT:
+        return np.full(x.shape, block[2]), np.zeros(x.shape), np.zeros(x.shape)
+    if kind == S.PHASE_LINEAR:
+        return block[2] * x + block[3] * y, np.full(x.shape, block[2]), np.full(x.shape, block[3])
+    if kind == S.PHASE_RADIAL:
+        r2 = x * x + y * y
+        a = block[3:3 + int(block[2])]
+        phi = sum(c * r2 ** (p + 1) for p, c in enumerate(a))
+        g = sum(2 * (p + 1) * c * r2 ** p for p, c in enumerate(a))
+        return phi, g * x, g * y
+    W, H, n_scale, nodes = _grid_fields(block)
+    scale = block[9 + wl_index] if n_scale else 1.0
+    ix, iy = grid_coordinates(block, x, y)
+    x0, y0 = np.floor(ix), np.floor(iy)
+
+    def node(col, row):
+        inside = (col >= 0) & (col <= W - 1) & (row >= 0) & (row <= H - 1)
+        c = np.clip(col, 0, W - 1).astype(int)
+        r = np.clip(row, 0, H - 1).astype(int)
+        return np.where(inside, nodes[r, c], 0.0)
+
+    v00, v01, v10, v11 = node(x0, y0), node(x0 + 1, y0), node(x0, y0 + 1), node(x0 + 1, y0 + 1)
+    tx, ty = ix - x0, iy - y0
+    phi = v00 * (1 - tx) * (1 - ty) + v01 * tx * (1 - ty) + v10 * (1 - tx) * ty + v11 * tx * ty
+    gx = ((v01 - v00) * (1 - ty) + (v11 - v10) * ty) * (W - 1) / (block[5] - block[4])
+    gy = ((v10 - v00) * (1 - tx) + (v11 - v01) * tx) * (H - 1) / (block[7] - block[6])
+    return scale * phi, scale * gx, scale * gy
+
+
+def local_hit(table: SystemTable, g: int, after: np.ndarray):
+    """(x, y) of the recorded hit (8, n) in the frame of row `g`."""
+    row = table.surfaces[g]
+    R = np.asarray(row["rot"], dtype=np.float64).reshape(3, 3)
+    p = R @ (after[:3] - np.asarray(row["origin"], dtype=np.float64)[:, None])
+    return p[0], p[1]
+
+
+def radicand(table: SystemTable, g: int, before: np.ndarray, after: np.ndarray,
+             wl_index: int = 0) -> np.ndarray:
+    """S / n2'^2 per ray of the phase row `g`: from the state in front of the surface (8, n) and
+    the recorded hit behind it (8, n), both in the global frame."""
+    row = table.surfaces[g]
+    R = np.asarray(row["rot"], dtype=np.float64).reshape(3, 3)
+    k0 = R @ before[3:6]
+    x, y = local_hit(table, g, after)
+    n1 = float(table.optics["n1"][g, wl_index])
+    n2 = n1 if int(row["interaction"]) == S.INTERACT_REFLECT else \
+        float(table.optics["n2"][g, wl_index])
+    q = float(table.wavelengths[wl_index]) * 1e-3 / (2 * np.pi)
+    _phi, gx, gy = profile_numpy(block_of(table, g), wl_index, x, y)
+    tx, ty = n1 * k0[0] + q * gx, n1 * k0[1] + q * gy
+    return (n2 * n2 - tx * tx - ty * ty) / (n2 * n2)
+
+
+# ------------------------------------------------------------------ the fixture
+@functools.lru_cache(maxsize=None)
+def golden():
+    with np.load(GOLD) as z:
+        return {k: z[k] for k in z.files}
+
+
+def case_names():
+    return [str(c) for c in golden()["cases"]]
+
+
+@functools.lru_cache(maxsize=None)
+def case(name: str) -> dict:
+    """One case: `table`, `g` (the phase row), `wl` (wavelength index), `rows` (S + 1, 8, n) --
+    what every surface recorded of the reference's `SurfaceGroup.trace`, row 0 the object
+    surface's -- `dropped` ((2,): rays dropped at the radicand and at grid lines, of 127) and, in
+    the BIG_CASES, `big_in` / `big_out` (8, 1027 or fewer).  Treat as read-only."""
+    gd = golden()
+    out = {k.split("/", 1)[1]: gd[k] for k in gd if k.startswith(name + "/")}
+    out["name"] = name
+    out["table"] = SystemTable.from_json(str(out["table"]))
+    out["g"], out["wl"] = int(out["g"]), int(out["wl"])
+    for k in ("rows", "big_in", "big_out"):
+        if k in out:
+            out[k].setflags(write=False)
+    return out
+
+
+# ------------------------------------------------------------------ tests/hostphase
+def _builder():
+    spec = importlib.util.spec_from_file_location(
+        "_hostphase_build", os.path.join(HERE, "hostphase", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def write_case(path, table: SystemTable, planes, surface: int, fp64: bool = True,
+               wl_index: int = 0) -> None:
+    """The flat file tests/hostphase/main.hip reads (its header comment has the layout)."""
+    surf = np.ascontiguousarray(table.surfaces)
+    optics = np.ascontiguousarray(table.optics)
+    coeffs = np.ascontiguousarray(table.coeffs, dtype=np.float64)
+    planes = np.ascontiguousarray(planes, dtype="<f8")
+    assert planes.shape[0] == 8
+    head = np.array([MAGIC, surf.shape[0], optics.shape[1], coeffs.size, planes.shape[1], surface,
+                     wl_index, int(fp64)], dtype="<i8")
+    wl = np.array([float(table.wavelengths[wl_index])], dtype="<f8")
+    with open(path, "wb") as f:
+        for a in (head, wl, surf, optics, coeffs, planes):
+            f.write(np.ascontiguousarray(a).tobytes())
+
+
+def host_step(exe: str, path):
+    """(8, n) of `hostphase step`, and the OR of the rays' status bits."""
+    out, bits = [], 0
+    for line in run_host(exe, "step", path).splitlines():
+        part = line.split()
+        assert part[0] == "ray", line
+        out.append([float(v) for v in part[2:10]])
+        bits |= int(part[10])
+    return np.array(out, dtype=np.float64).reshape(-1, 8).T.copy(), bits
+
+
+# ------------------------------------------------------------------ CPU stand-in of the engine
+def make_engine_class(exe: str, tmp_dir):
+    """`OracleEngine` (tests/_fake_engine.py) for the fused runs + the host checker for the phase
+    rows, joined by the product's own splitter (`optiland_amd.engine.split_trace`): what
+    `HipSystem.trace` does on a range with phase rows, on CPU tensors."""
+    import torch
+
+    from optiland_amd.engine import TraceResult, split_trace
+    from tests._fake_engine import OracleEngine
+
+    class PhaseOracleEngine(OracleEngine):
+        phase_launches = 0
+
+        def can_trace_phase(self):
+            return True
+
+        def trace_phase(self, rays, surface, wavelength_index=0, record_row=None,
+                        write_rays=None, midrange=False, **_):
+            type(self).phase_launches += 1
+            n = int(rays[0].numel())
+            path = os.path.join(str(tmp_dir), f"engine_{id(self)}.case")
+            write_case(path, self.table, np.stack([t.double().numpy() for t in rays]),
+                       surface=int(surface), wl_index=int(wavelength_index))
+            got, _bits = host_step(exe, path)
+            new = torch.as_tensor(got, dtype=rays[0].dtype)
+            if record_row is not None:
+                record_row[:, :n].copy_(new)
+            if write_rays or (write_rays is None and record_row is None):
+                for k in range(8):
+                    rays[k].copy_(new[k])
+            return 0
+
+        def trace(self, rays, wavelength_index=0, record=True, prt=None, first=0, last=None,
+                  write_rays=None, check_status=True, prt_identity=False,
+                  nonunit_directions=False):
+            last = self.num_surfaces - 1 if last is None else last
+            if not any(first <= f <= last for f in self.table.phases):
+                return super().trace(rays, wavelength_index, record, prt, first, last, write_rays,
+                                     check_status, prt_identity, nonunit_directions)
+            assert prt is None, "the bridge keeps polarised bundles off the phase kernel"
+            rays = list(rays)
+            n = int(rays[0].numel())
+            rec = record if isinstance(record, torch.Tensor) else (
+                self.alloc_record(n, rays[0].dtype, last - first + 1) if record is True else None)
+            if write_rays is None:
+                write_rays = rec is None
+            work = rays if write_rays else [t.clone() for t in rays]
+            base = super()
+
+            def fused(a, b, view, r0, midrange):
+                assert r0 is None or r0 == a
+                base.trace(work, wavelength_index, record=view if view is not None else False,
+                           first=a, last=b, write_rays=True)
+
+            def one(s, row, midrange):
+                self.trace_phase(work, s, wavelength_index, record_row=row, write_rays=True,
+                                 midrange=midrange)
+
+            split_trace(self.table.phases, first, last, rec, first, fused, one)
+            return TraceResult(n, rays, rec, None, 0, first, last)
+
+    return PhaseOracleEngine
