@@ -118,6 +118,23 @@ enum { OL_F32 = 0, OL_F64 = 1 };
  *               Phase rows are traced by ol_trace_phase ONLY, one surface per launch: the entry
  *               points listed for the Forbes rows return OL_EUNSUPPORTED, naming the surface,
  *               when their range holds one.  (Additive, like the Forbes kinds.)
+ * GRID_SAG      optiland/geometries/grid_sag.py (surface type "grid_sag": a measured or freeform
+ *               surface): the sag is the bilinear interpolant of a table of sag values over two
+ *               strictly increasing coordinate vectors, which need not be uniform; the hit is a
+ *               Newton-Raphson solve from t = 0 with the row's `tol` (on |dt|) and `max_iter`; a
+ *               ray whose iterate leaves [x_0, x_{W-1}] x [y_0, y_{H-1}] leaves the surface with
+ *               NaN position and direction.  radius and conic are not read.  The coefficient
+ *               block describes itself; all values are doubles, counts are whole numbers stored
+ *               as doubles:
+ *                 [0] W  [1] H, then W x-coordinates, then H y-coordinates, then H * W sag
+ *                 values, row-major, row = y index (the reference's sag_grid[j, i])
+ *               2 <= W, H <= 2^24; 2 + W + H + H * W = n_coeff exactly; every value finite; both
+ *               coordinate vectors strictly increasing, also after rounding to float.  The cell
+ *               of a point is the reference's: i the largest index with x_i <= x, clamped to
+ *               [0, W - 2], taken from the stored coordinates; j likewise.
+ *               Grid-sag rows are traced by ol_trace_grid_sag ONLY, one surface per launch: the
+ *               entry points listed for the Forbes rows return OL_EUNSUPPORTED, naming the
+ *               surface, when their range holds one.  (Additive, like the Forbes kinds.)
  */
 typedef enum ol_geom_kind {
   OL_GEOM_PLANE = 0,
@@ -134,7 +151,9 @@ typedef enum ol_geom_kind {
   OL_GEOM_PLANE_GRATING = 11,
   OL_GEOM_STANDARD_GRATING = 12,
   /* 13 is not a kind: ol_system_create has always refused it as unknown and still does */
-  OL_GEOM_PLANE_PHASE = 14
+  OL_GEOM_PLANE_PHASE = 14,
+  /* 15 and 17 are not kinds either: refused as unknown, as they always were */
+  OL_GEOM_GRID_SAG = 16
 } ol_geom_kind;
 
 /* ---- what happens at the surface ----------------------------------------
@@ -473,6 +492,18 @@ int ol_trace_phase(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* cons
                    int32_t wavelength_index, double wavelength_um, void* record_row,
                    int64_t record_stride, int32_t surface, uint32_t flags, uint32_t* status,
                    void* stream);
+
+/* ONE grid-sag surface (OL_GEOM_GRID_SAG) in one launch: what Surface.trace does there
+ * (surfaces/standard_surface.py:232-274 with geometries/grid_sag.py) -- into the surface's frame,
+ * the Newton-Raphson solve on the bilinear interpolant from t = 0, stopped per ray when
+ * |dt| < tol, propagation, absorption, OPD, aperture clip, the normal (-ds/dx, -ds/dy, 1) / |.| at
+ * the hit, refraction or reflection, SimpleCoating, back to the global frame.  A ray that leaves
+ * the grid comes out with NaN position and direction and raises OL_STATUS_NAN_DIRECTION (not with
+ * OL_TRACE_MIDRANGE).  Unpolarised only.  Arguments, flags and status as for ol_trace_forbes:
+ *   surface           index of the grid-sag row (OL_EINVAL for any other geometry kind)         */
+int ol_trace_grid_sag(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const rays[8],
+                      int32_t wavelength_index, void* record_row, int64_t record_stride,
+                      int32_t surface, uint32_t flags, uint32_t* status, void* stream);
 
 /* ABI 11.  The iteration count of ONE reference-rule Newton surface for this batch of rays
  * (see OL_SURF_REFERENCE_NEWTON): the rays are traced from `first_surface` up to `surface` --

@@ -12,6 +12,7 @@ import os
 from . import build as _build
 from .system import GEOM_PLANE_GRATING, GEOM_STANDARD_GRATING  # noqa: F401 - OL_GEOM_*_GRATING
 from .system import GEOM_PLANE_PHASE  # noqa: F401 - OL_GEOM_PLANE_PHASE
+from .system import GEOM_GRID_SAG  # noqa: F401 - OL_GEOM_GRID_SAG
 
 _LIB = None
 
@@ -156,6 +157,7 @@ EXPORTS = (
     "ol_trace_forbes",
     "ol_trace_grating",
     "ol_trace_phase",
+    "ol_trace_grid_sag",
 )
 
 F32, F64 = 0, 1
@@ -322,6 +324,10 @@ def bind(lib, path: str = "?"):
         lib.ol_trace_phase.restype = C.c_int
         lib.ol_trace_phase.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, C.c_double, vp, i64,
                                        i32, u32, vp, vp]
+    if has_trace_grid_sag(lib):   # (additive within ABI 11, like ol_trace_forbes)
+        lib.ol_trace_grid_sag.restype = C.c_int
+        lib.ol_trace_grid_sag.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, vp, i64, i32, u32,
+                                          vp, vp]
     return lib
 
 
@@ -382,6 +388,11 @@ def has_trace_grating(lib) -> bool:
 def has_trace_phase(lib) -> bool:
     """True when the loaded library exports ol_trace_phase."""
     return hasattr(lib, "ol_trace_phase")
+
+
+def has_trace_grid_sag(lib) -> bool:
+    """True when the loaded library exports ol_trace_grid_sag."""
+    return hasattr(lib, "ol_trace_grid_sag")
 
 
 def has_huygens(lib) -> bool:

@@ -859,6 +859,58 @@ int stage_phase_block(int32_t i, const ol_surface_desc& s, const double* src, in
   return OL_OK;
 }
 
+// The self-describing block of an OL_GEOM_GRID_SAG row (ol_geom_kind in optiland_hip.h), checked
+// value by value and appended to `out` in the layout grid_sag_device.h reads.  src: the row's
+// s.n_coeff values (inside the buffer: the caller checked the range).
+int stage_grid_sag_block(int32_t i, const ol_surface_desc& s, const double* src,
+                         std::vector<double>& out, std::vector<size_t>& int_slots) {
+  const int64_t n = s.n_coeff;
+  auto whole = [&](double c, int64_t& v) {
+    if (!(c >= 0.0) || c > (double)n || c != std::floor(c)) return false;
+    v = (int64_t)c;
+    return true;
+  };
+  if (s.interaction == OL_INTERACT_RECORD_ONLY)
+    return failf(OL_EUNSUPPORTED, "surface %d: a grid-sag surface that only records", i);
+  int64_t W = 0, H = 0;
+  if (n < 2 || !whole(src[0], W) || !whole(src[1], H) || W < 2 || H < 2)
+    return failf(OL_EINVAL, "surface %d: a sag grid needs whole node counts W, H >= 2 (got %g, "
+                            "%g)", i, n >= 2 ? src[0] : -1.0, n >= 2 ? src[1] : -1.0);
+  // (the last cell, W - 2, is a float in the fp32 table: exact up to 2^24)
+  if (W > (1 << 24) || H > (1 << 24))
+    return failf(OL_EINVAL, "surface %d: a sag grid takes at most 16777216 nodes on an axis (got "
+                            "%lld, %lld)", i, (long long)W, (long long)H);
+  if (2 + W + H + W * H != n)
+    return failf(OL_EINVAL, "surface %d: sag grid block of %lld values does not match the counts "
+                            "it declares (2 + %lld + %lld coordinates + %lld x %lld nodes)", i,
+                 (long long)n, (long long)W, (long long)H, (long long)W, (long long)H);
+  for (int64_t k = 2; k < n; ++k)
+    if (!std::isfinite(src[k]))
+      return failf(OL_EINVAL, "surface %d: sag grid value %lld (%g) is not finite", i,
+                   (long long)k, src[k]);
+  const double* xs = src + 2;
+  const double* ys = xs + W;
+  auto increasing = [&](const double* v, int64_t cnt, const char* axis) {
+    for (int64_t k = 1; k < cnt; ++k)
+      if (!(v[k] > v[k - 1]) || !((float)v[k] > (float)v[k - 1]))
+        return failf(OL_EINVAL, "surface %d: sag grid %s coordinates are not strictly increasing "
+                                "(as doubles and as floats) at index %lld: %.17g, %.17g", i, axis,
+                     (long long)k, v[k - 1], v[k]);
+    return (int)OL_OK;
+  };
+  if (int rc = increasing(xs, W, "x")) return rc;
+  if (int rc = increasing(ys, H, "y")) return rc;
+  const size_t base = out.size();
+  const double head[ol::kGridSagHead] = {
+      (double)W, (double)H, (double)(W - 2), (double)(H - 2), xs[0], xs[W - 1], ys[0], ys[H - 1],
+      (double)(W - 1) / (xs[W - 1] - xs[0]), (double)(H - 1) / (ys[H - 1] - ys[0])};
+  out.insert(out.end(), head, head + ol::kGridSagHead);
+  int_slots.push_back(base);
+  int_slots.push_back(base + 1);
+  out.insert(out.end(), src + 2, src + n);
+  return OL_OK;
+}
+
 // argument validation + every host-side conversion of ol_system_create / ol_system_update
 int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
                  const double* coeffs, int32_t n_coeffs, const ol_surface_optics* optics,
@@ -877,8 +929,8 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     const ol_surface_desc& s = surf[i];
     HostSurf& d = dev[i];
     std::memset(&d, 0, sizeof(d));
-    if (s.geom_kind < OL_GEOM_PLANE || s.geom_kind > OL_GEOM_PLANE_PHASE ||
-        s.geom_kind == 13)   // (13: never assigned, refused as it always was)
+    if (s.geom_kind < OL_GEOM_PLANE || s.geom_kind > OL_GEOM_GRID_SAG ||
+        s.geom_kind == 13 || s.geom_kind == 15)   // (13, 15: never assigned, refused as always)
       return failf(OL_EUNSUPPORTED, "surface %d: geometry kind %d", i, s.geom_kind);
     if (s.interaction < OL_INTERACT_RECORD_ONLY || s.interaction > OL_INTERACT_REFLECT)
       return failf(OL_EUNSUPPORTED, "surface %d: interaction %d", i, s.interaction);
@@ -899,6 +951,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     if (s.geom_kind == OL_GEOM_PLANE_GRATING) d.geom = ol::kGeomPlaneGrating;
     if (s.geom_kind == OL_GEOM_STANDARD_GRATING) d.geom = ol::kGeomStandardGrating;
     if (s.geom_kind == OL_GEOM_PLANE_PHASE) d.geom = ol::kGeomPlanePhase;
+    if (s.geom_kind == OL_GEOM_GRID_SAG) d.geom = ol::kGeomGridSag;
     d.interaction = s.interaction;
     d.aperture_kind = s.aperture_kind;
     d.coating_kind = s.coating_kind;
@@ -906,7 +959,8 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
     d.poly_cols = s.poly_cols;
     d.flags = (s.flags & OL_SURF_ROTATED) ? ol::kSurfRotated : 0u;
     const bool inf_r = std::isinf(s.radius) || s.geom_kind == OL_GEOM_PLANE ||
-                       s.geom_kind == OL_GEOM_PLANE_GRATING || s.geom_kind == OL_GEOM_PLANE_PHASE;
+                       s.geom_kind == OL_GEOM_PLANE_GRATING || s.geom_kind == OL_GEOM_PLANE_PHASE ||
+                       s.geom_kind == OL_GEOM_GRID_SAG;   // (a grid has no base conic)
     if (inf_r) d.flags |= ol::kSurfRadiusInf;
     if ((s.flags & OL_SURF_REFERENCE_ROOT) && !inf_r &&
         (s.geom_kind == OL_GEOM_STANDARD || s.geom_kind == OL_GEOM_STANDARD_GRATING))
@@ -1125,6 +1179,10 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
       // public block (ol_geom_kind, include/optiland_hip.h) -> device block (phase_device.h)
       if (int rc = stage_phase_block(i, s, src, n_wavelengths, dcoef, int_slots)) return rc;
       d.n_coeff = s.n_coeff;
+    } else if (ol::is_grid_sag_kind(s.geom_kind)) {
+      // public block (ol_geom_kind, include/optiland_hip.h) -> device block (grid_sag_device.h)
+      if (int rc = stage_grid_sag_block(i, s, src, dcoef, int_slots)) return rc;
+      d.n_coeff = s.n_coeff;
     } else {
       d.n_coeff = 0;
     }
@@ -1165,6 +1223,7 @@ int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
                                     surf[i].geom_kind != OL_GEOM_STANDARD &&
                                     !ol::is_grating_kind(surf[i].geom_kind) &&
                                     !ol::is_phase_kind(surf[i].geom_kind) &&
+                                    !ol::is_grid_sag_kind(surf[i].geom_kind) &&
                                     surf[i].interaction != OL_INTERACT_RECORD_ONLY
                                 ? 1 : 0);
   }
@@ -1272,6 +1331,7 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const r
   if (int rc = rule_no_forbes("ol_trace", v, first_surface, last_surface)) return rc;
   if (int rc = rule_no_grating("ol_trace", v, first_surface, last_surface)) return rc;
   if (int rc = rule_no_phase("ol_trace", v, first_surface, last_surface)) return rc;
+  if (int rc = rule_no_grid_sag("ol_trace", v, first_surface, last_surface)) return rc;
   if (n_rays == 0) return OL_OK;
   if (int rc = rule_current_device("ol_trace", v)) return rc;
   if (int rc = rule_planes("ol_trace", "rays", rays, 8)) return rc;
@@ -1310,6 +1370,7 @@ int ol_newton_count(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* con
   if (int rc = rule_no_forbes("ol_newton_count", v, first_surface, surface)) return rc;
   if (int rc = rule_no_grating("ol_newton_count", v, first_surface, surface)) return rc;
   if (int rc = rule_no_phase("ol_newton_count", v, first_surface, surface)) return rc;
+  if (int rc = rule_no_grid_sag("ol_newton_count", v, first_surface, surface)) return rc;
   if (!v.ref_newton[surface])
     return failf(OL_EINVAL, "ol_newton_count: surface %d is not a traced Newton-Raphson surface "
                             "with OL_SURF_REFERENCE_NEWTON", surface);

@@ -102,8 +102,13 @@ enum : int {
   kGeomStandardGrating = 19,
   // OL_GEOM_PLANE_PHASE (14), renumbered likewise: traced by phase.hip alone (phase_device.h,
   // which has the layout of the block)
-  kGeomPlanePhase = 20
+  kGeomPlanePhase = 20,
+  // OL_GEOM_GRID_SAG (16), renumbered likewise: traced by grid_sag.hip alone (grid_sag_device.h,
+  // which has the layout of the block)
+  kGeomGridSag = 21
 };
+// values of a kGeomGridSag block in front of its coordinate vectors (grid_sag_device.h)
+constexpr int kGridSagHead = 10;
 // profile kinds of a kGeomPlanePhase block ([0] of it) and the values of a grid block in front of
 // its scales (phase_device.h)
 enum : int { kPhaseConstant = 0, kPhaseLinear = 1, kPhaseRadial = 2, kPhaseGrid = 3 };

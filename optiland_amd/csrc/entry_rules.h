@@ -123,12 +123,23 @@ inline int rule_no_phase(const char* who, const SystemView& v, int32_t first, in
   return OL_OK;
 }
 
+// grid-sag rows (OL_GEOM_GRID_SAG) likewise: ol_trace_grid_sag alone (grid_sag.hip) knows the
+// table of sag values, the fused kernels have no functor for it
+inline int rule_no_grid_sag(const char* who, const SystemView& v, int32_t first, int32_t last) {
+  for (int32_t s = first; s <= last; ++s)
+    if (is_grid_sag_kind(v.geom[s]))
+      return failf(OL_EUNSUPPORTED, "%s: surface %d is a grid-sag surface: trace it with "
+                                    "ol_trace_grid_sag and cut the range there", who, s);
+  return OL_OK;
+}
+
 // the fused entry points (one launch: generate -> trace [-> reduce]) walk the whole system and do
 // not serve ranges whose Newton iteration count is a property of the batch
 inline int rule_no_reference_newton(const char* who, const SystemView& v) {
   if (int rc = rule_no_forbes(who, v, 0, v.n_surf - 1)) return rc;
   if (int rc = rule_no_grating(who, v, 0, v.n_surf - 1)) return rc;
   if (int rc = rule_no_phase(who, v, 0, v.n_surf - 1)) return rc;
+  if (int rc = rule_no_grid_sag(who, v, 0, v.n_surf - 1)) return rc;
   for (int32_t s = 0; s < v.n_surf; ++s)
     if (v.ref_newton[s])
       return failf(OL_EUNSUPPORTED, "%s: the system carries OL_SURF_REFERENCE_NEWTON surfaces "

@@ -52,6 +52,10 @@ inline int aim_check(const ol_system* sys, int64_t n_rays, int32_t wavelength_in
     if (is_phase_kind(v.geom[s]))
       return failf(OL_EUNSUPPORTED, "ol_aim_rays: surface %d is a phase surface (traced by "
                                     "ol_trace_phase only)", s);
+  for (int32_t s = first_surface; s <= stop_surface; ++s)
+    if (is_grid_sag_kind(v.geom[s]))
+      return failf(OL_EUNSUPPORTED, "ol_aim_rays: surface %d is a grid-sag surface (traced by "
+                                    "ol_trace_grid_sag only)", s);
   // a batch-global stop rule has no per-ray form
   for (int32_t s = first_surface; s <= stop_surface; ++s)
     if (v.ref_newton[s])

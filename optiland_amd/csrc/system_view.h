@@ -23,7 +23,7 @@ struct SystemView {
   const int32_t* coating;
   const uint8_t* ref_newton;         // OL_SURF_REFERENCE_NEWTON on a traced Newton surface
   const int32_t* geom;               // ol_geom_kind as given, [n_surf]
-  const DevSurfHot<float>* surf32;   // the fp32 table (forbes.hip, grating.hip, phase.hip)
+  const DevSurfHot<float>* surf32;   // the fp32 table (the one-surface units: forbes.hip, ...)
   const DevSurfCold<float>* cold32;
   const DevOptics<float>* optics32;
   const float* coeffs32;
@@ -34,6 +34,7 @@ inline bool is_grating_kind(int32_t g) {
   return g == OL_GEOM_PLANE_GRATING || g == OL_GEOM_STANDARD_GRATING;
 }
 inline bool is_phase_kind(int32_t g) { return g == OL_GEOM_PLANE_PHASE; }
+inline bool is_grid_sag_kind(int32_t g) { return g == OL_GEOM_GRID_SAG; }
 
 // `sys` must not be NULL
 SystemView system_view(const ol_system* sys);

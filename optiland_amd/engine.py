@@ -810,9 +810,10 @@ class HipSystem:
               spot=None, record_first: int | None = None,
               nonunit_directions: bool = False, _status_to=None) -> TraceResult:
         """Launch the fused trace.  A range that holds Forbes rows (`table.forbes`), grating
-        rows (`table.gratings`) or phase rows (`table.phases`) is split into fused runs and one
-        `trace_forbes` / `trace_grating` / `trace_phase` launch per such row, all writing into the
-        same record block and status word (unpolarised, no spot epilogue).
+        rows (`table.gratings`), phase rows (`table.phases`) or grid-sag rows
+        (`table.grid_sag_rows`) is split into fused runs and one `trace_forbes` / `trace_grating` /
+        `trace_phase` / `trace_grid_sag` launch per such row, all writing into the same record
+        block and status word (unpolarised, no spot epilogue).
 
         rays: sequence of 8 contiguous 1-D device tensors (x,y,z,L,M,N,i,opd) of one
         dtype -- the initial state.  record: True (allocate), False/None, or a
@@ -857,12 +858,13 @@ class HipSystem:
                 raise ValueError("record must be a contiguous (rows, 8, stride>=n) tensor")
         if write_rays is None:
             write_rays = rec is None
-        singles = self.table.forbes + self.table.gratings + self.table.phases
+        singles = self.table.forbes + self.table.gratings + self.table.phases \
+            + self.table.grid_sag_rows
         if singles and any(first <= f <= last for f in singles):
             if prt is not None or spot is not None:
-                raise ValueError("a range with Forbes surfaces, gratings or phase surfaces is "
-                                 "traced unpolarised and without the spot epilogue (cut it at "
-                                 "those surfaces)")
+                raise ValueError("a range with Forbes surfaces, gratings, phase surfaces or "
+                                 "grid-sag surfaces is traced unpolarised and without the spot "
+                                 "epilogue (cut it at those surfaces)")
             return self._trace_split(rays, int(wavelength_index), rec, rec_first, int(first),
                                      int(last), write_rays, check_status, defer_status,
                                      zero_status)
@@ -988,11 +990,31 @@ class HipSystem:
                                   record_row, write_rays, midrange, check_status, defer_status,
                                   zero_status)
 
+    # ---- grid-sag surfaces (ol_trace_grid_sag: one surface, one launch) ------------------------
+    def can_trace_grid_sag(self) -> bool:
+        return _capi.has_trace_grid_sag(self.lib)
+
+    def trace_grid_sag(self, rays, surface: int, wavelength_index: int = 0, record_row=None,
+                       write_rays: bool | None = None, midrange: bool = False,
+                       check_status: bool = True, defer_status: bool = False,
+                       zero_status: bool = True) -> int:
+        """`trace_forbes` for the ONE grid-sag row `surface` of the table (`ol_trace_grid_sag`):
+        frame change, the Newton solve on the bilinear interpolant of the sag table from t = 0,
+        stopped per ray, interaction, back to the global frame.  A ray that leaves the grid comes
+        out with NaN position and direction (STATUS_NAN_DIRECTION unless midrange), as in the
+        reference.  A missing kernel is an error."""
+        if not self.can_trace_grid_sag():
+            raise _capi.HipExtensionError("the loaded library has no ol_trace_grid_sag: rebuild it")
+        return self._trace_single("ol_trace_grid_sag", (), self.table.grid_sag_rows, "a grid-sag",
+                                  rays, surface, wavelength_index,
+                                  record_row, write_rays, midrange, check_status, defer_status,
+                                  zero_status)
+
     def _trace_single(self, entry, extra, rows, kind, rays, surface, wavelength_index, record_row,
                       write_rays, midrange, check_status, defer_status, zero_status) -> int:
-        """The launch `trace_forbes`, `trace_grating` and `trace_phase` share: `entry` takes `extra` behind the
-        wavelength index and serves the table's `rows` ("`kind` row"), everything else alike --
-        the checks in the order `trace_forbes` always made them."""
+        """The launch `trace_forbes`, `trace_grating`, `trace_phase` and `trace_grid_sag` share:
+        `entry` takes `extra` behind the wavelength index and serves the table's `rows` ("`kind`
+        row"), everything else alike -- the checks in the order `trace_forbes` always made them."""
         rays = list(rays)
         if len(rays) != 8:
             raise ValueError("rays must be 8 planes: x,y,z,L,M,N,i,opd")
@@ -1053,15 +1075,17 @@ class HipSystem:
                        _status_to=word)
 
         gratings, phases = set(self.table.gratings), set(self.table.phases)
+        grid_sags = set(self.table.grid_sag_rows)
 
         def one(s, row, midrange):
             launch = self.trace_grating if s in gratings else \
-                self.trace_phase if s in phases else self.trace_forbes
+                self.trace_phase if s in phases else \
+                self.trace_grid_sag if s in grid_sags else self.trace_forbes
             launch(work, s, wl, record_row=row, write_rays=True, midrange=midrange,
                    check_status=check_status, defer_status=True, zero_status=False)
 
-        split_trace(self.table.forbes + self.table.gratings + self.table.phases, first, last, rec,
-                    rec_first, fused, one)
+        split_trace(self.table.forbes + self.table.gratings + self.table.phases
+                    + self.table.grid_sag_rows, first, last, rec, rec_first, fused, one)
         if mid:
             self._status.bitwise_or_(mid[0].bitwise_and_(~S.STATUS_NAN_DIRECTION))
         status = int(self._status.item()) if (check_status and not defer_status) else 0

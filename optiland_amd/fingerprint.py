@@ -256,6 +256,13 @@ def _phase_terms(im, keep, memo=None):
             _material(m, keep, {} if memo is None else memo) if hasattr(m, "__dict__") else None)
 
 
+# (A grid-sag geometry -- geometries/grid_sag.py -- needs no walk of its own: x_grid, y_grid,
+# sag_grid, tol and max_iter, all the packer reads of it, are arrays and scalars of the geometry's
+# own `__dict__`, which the one-level walk tokenises -- arrays by content, tensors by identity and
+# `_version`.  A GridSagVariable update (optimization/variable/grid_sag.py) assigns a new
+# `sag_grid` and so re-packs; tests/test_grid_sag_cpu.py holds that.)
+
+
 def _surface_token_py(s, keep, memo):
     geom = s.geometry
     im = getattr(s, "interaction_model", None)

@@ -960,7 +960,9 @@ _SG = {"device": None, "force": False, "count": 0, "fallbacks": 0, "foreign": 0,
        # enable(gratings=...): diffraction gratings as device work (OPTILAND_HIP_GRATINGS=0: off)
        "gratings": os.environ.get("OPTILAND_HIP_GRATINGS", "1") != "0",
        # enable(phases=...): phase-profile planes likewise (OPTILAND_HIP_PHASES=0: off)
-       "phases": os.environ.get("OPTILAND_HIP_PHASES", "1") != "0"}
+       "phases": os.environ.get("OPTILAND_HIP_PHASES", "1") != "0",
+       # enable(grid_sags=...): grid-sag surfaces likewise (OPTILAND_HIP_GRID_SAGS=0: off)
+       "grid_sags": os.environ.get("OPTILAND_HIP_GRID_SAGS", "1") != "0"}
 # settings of the class-wide patch (enable())
 _ENABLE = {"device": None, "force": False, "lazy": False}
 _PLANE_ATTRS = ("x", "y", "z", "L", "M", "N", "i", "opd")
@@ -1010,25 +1012,28 @@ def _sg_table(group, wavelength):
     before packing, so that the production path packs once and a stand-in factory that knows
     nothing of gratings gets the table -- and the reference's own surface -- it always got.
     Phase-profile planes (`table.phases`) likewise: `traces_phases`, `enable(phases=False)` /
-    OPTILAND_HIP_PHASES=0."""
+    OPTILAND_HIP_PHASES=0.  Grid-sag surfaces (`table.grid_sag_rows`) likewise:
+    `traces_grid_sags`, `enable(grid_sags=False)` / OPTILAND_HIP_GRID_SAGS=0."""
     gratings = bool(_SG["gratings"]) and bool(getattr(_tracer._make_engine, "traces_gratings",
                                                       False))
     phases = bool(_SG["phases"]) and bool(getattr(_tracer._make_engine, "traces_phases", False))
+    grid_sags = bool(_SG["grid_sags"]) and bool(getattr(_tracer._make_engine, "traces_grid_sags",
+                                                        False))
     tok = None
     if _fp.ENABLED:
         tok, _keep = _fp.surfaces_token(group.surfaces, wavelength)
         memo = group.__dict__.get("_hip_sg_memo")
         memo = memo.value if memo is not None else None
-        if memo is not None and memo[0] == tok and memo[3] == (gratings, phases):
+        if memo is not None and memo[0] == tok and memo[3] == (gratings, phases, grid_sags):
             return memo[2]
     try:
         table = pack_surfaces(group.surfaces, [wavelength], name="SurfaceGroup", tolerate=True,
-                              gratings=gratings, phases=phases)
+                              gratings=gratings, phases=phases, grid_sags=grid_sags)
     except UnsupportedSystem:
         table = None
     if tok is not None:
         tok, keep = _fp.surfaces_token(group.surfaces, wavelength)  # after the pack
-        group.__dict__["_hip_sg_memo"] = _Volatile((tok, keep, table, (gratings, phases)))
+        group.__dict__["_hip_sg_memo"] = _Volatile((tok, keep, table, (gratings, phases, grid_sags)))
     return table
 
 
@@ -1122,7 +1127,7 @@ def _hip_surface_group_trace(group, rays, skip):
     from its CURRENT value (rays/polarized_rays.py:180-202).
 
     Surfaces the fused path does not implement (thin lens, NURBS
-    / grid-sag geometry, GRIN media, BSDF, thin-film coating ...) do not disqualify the
+    geometry, GRIN media, BSDF, thin-film coating ...) do not disqualify the
     whole system: they are traced by their own `Surface.trace(rays)` on the same device
     tensors, and the runs of supported surfaces between them are one launch each
     (`ol_trace`'s [first, last] range; SURVEY.md section 8b "split the system into supported
@@ -1146,7 +1151,14 @@ def _hip_surface_group_trace(group, rays, skip):
     profiles of optiland/phase/) are the same again: one `ol_trace_phase` launch inside a run,
     served, a polarised bundle excepted; packed as such only for an engine that traces them and
     while `enable(phases=False)` has not switched them off.  The gridded profiles reproduce the
-    TORCH backend's bilinear interpolant, whatever backend is active."""
+    TORCH backend's bilinear interpolant, whatever backend is active.
+
+    Grid-sag surfaces (`table.grid_sag_rows`: the reference's GridSagGeometry itself with the
+    refracting / reflecting model) are the same again: one `ol_trace_grid_sag` launch inside a
+    run -- the reference's Python Newton loop of up to 100 passes with a host synchronisation each
+    -- served, a polarised bundle excepted; packed as such only for an engine that traces them,
+    while `enable(grid_sags=False)` has not switched them off and `reference_newton` is off (the
+    batch-wide stop rule is the reference's own loop)."""
     import optiland.backend as be
     from optiland.rays import PolarizedRays as RefPolarizedRays
     from optiland.rays import RealRays as RefRealRays
@@ -1170,7 +1182,8 @@ def _hip_surface_group_trace(group, rays, skip):
         return None
     foreign = set(table.unsupported)
     if polarized:
-        foreign |= set(table.forbes) | set(table.gratings) | set(table.phases)
+        foreign |= set(table.forbes) | set(table.gratings) | set(table.phases) \
+            | set(table.grid_sag_rows)
     if len(foreign) >= n_s - skip - (1 if skip == 0 else 0):
         return None  # nothing but the object row would run fused
     if table.uses_polarization and not polarized:
@@ -1342,7 +1355,8 @@ def _set_reference_newton(reference_newton):
 
 
 def enable(device=None, force=False, analyses=True, lazy_records=False, placed_records=None,
-           reference_root=None, reference_newton=None, gratings=None, phases=None):
+           reference_root=None, reference_newton=None, gratings=None, phases=None,
+           grid_sags=None):
     """Route EVERY `Optic` (existing and future) through the HIP path.
 
     Patches `RealRayTracer.trace / trace_generic` (raytrace/real_ray_tracer.py:58-154)
@@ -1404,6 +1418,10 @@ def enable(device=None, force=False, analyses=True, lazy_records=False, placed_r
     `phases` (default on; None = leave as is, OPTILAND_HIP_PHASES=0 seeds it off): a plane with a
     phase profile (PhaseInteractionModel: metalens, diffractive or holographic element) is one
     `ol_trace_phase` launch between two fused runs.  False: the reference's own `Surface.trace`.
+
+    `grid_sags` (default on; None = leave as is, OPTILAND_HIP_GRID_SAGS=0 seeds it off): a surface
+    of type "grid_sag" (GridSagGeometry: a measured or freeform surface) is one
+    `ol_trace_grid_sag` launch between two fused runs.  False: the reference's own `Surface.trace`.
     """
     _set_record_pool(placed_records)
     _set_reference_root(reference_root)
@@ -1412,6 +1430,8 @@ def enable(device=None, force=False, analyses=True, lazy_records=False, placed_r
         _SG["gratings"] = bool(gratings)
     if phases is not None:
         _SG["phases"] = bool(phases)
+    if grid_sags is not None:
+        _SG["grid_sags"] = bool(grid_sags)
     cls = _make_tracer_class()
     from optiland.raytrace.real_ray_tracer import RealRayTracer
 

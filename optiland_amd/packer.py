@@ -357,7 +357,60 @@ def _pack_phase(surf, wl, row, coeffs: list) -> None:
     coeffs.extend(block)
 
 
-def _pack_geometry(geom, row, coeffs: list, forbes: bool = False, grating: bool = False):
+def _is_grid_sag(surf) -> bool:
+    """The reference's GridSagGeometry ITSELF (an exact class match: a subclass may interpolate
+    anything) with the refracting / reflecting interaction model."""
+    geom = surf.geometry
+    if type(geom).__name__ != "GridSagGeometry" \
+            or type(surf.interaction_model).__name__ != "RefractiveReflectiveModel":
+        return False
+    try:
+        from optiland.geometries.grid_sag import GridSagGeometry
+    except Exception:  # noqa: BLE001 - a reference without the geometry
+        return False
+    return type(geom) is GridSagGeometry
+
+
+def _pack_grid_sag(geom, row, coeffs: list) -> None:
+    """A grid-sag surface in full (tolerate mode only): the self-describing block of
+    OL_GEOM_GRID_SAG (include/optiland_hip.h).  Raises `UnsupportedSystem` for what stays with
+    the reference's own surface: values that are not finite, coordinates that are not strictly
+    increasing as doubles or as floats, a sag table whose shape does not match its coordinates,
+    fewer than 2 nodes on an axis, and the opt-in reference Newton rule (the batch-wide stop test
+    is the reference's own loop: grid_sag.py:108-129)."""
+    if S.OPTIONS["reference_newton"]:
+        raise UnsupportedSystem("grid-sag surface under the reference Newton rule")
+    try:
+        xs, ys = _grid64(geom.x_grid), _grid64(geom.y_grid)
+        z = _grid64(geom.sag_grid)
+        tol, max_iter = float(geom.tol), int(geom.max_iter)
+    except Exception as exc:  # noqa: BLE001 - a geometry the packer cannot read is the reference's
+        raise UnsupportedSystem(f"grid-sag geometry: {exc}") from exc
+    if xs.ndim != 1 or ys.ndim != 1 or xs.size < 2 or ys.size < 2:
+        raise UnsupportedSystem(f"sag grid on {ys.shape} x {xs.shape} coordinates: at least 2 "
+                                "nodes on each axis")
+    if z.shape != (ys.size, xs.size):
+        raise UnsupportedSystem(f"sag grid of shape {z.shape} on {ys.size} x {xs.size} "
+                                "coordinates")
+    if not (np.isfinite(xs).all() and np.isfinite(ys).all() and np.isfinite(z).all()
+            and math.isfinite(tol)):
+        raise UnsupportedSystem("sag grid with values that are not finite")
+    for v in (xs, ys):
+        with np.errstate(over="ignore"):
+            v32 = v.astype(np.float32)
+        if not ((np.diff(v) > 0).all() and (np.diff(v32) > 0).all()):
+            raise UnsupportedSystem("sag grid whose coordinates are not strictly increasing (as "
+                                    "doubles and as floats)")
+    row["geom_kind"] = S.GEOM_GRID_SAG
+    row["tol"] = tol
+    row["max_iter"] = max_iter
+    block = [float(xs.size), float(ys.size)] + xs.tolist() + ys.tolist() + z.reshape(-1).tolist()
+    row["n_coeff"] = len(block)
+    coeffs.extend(block)
+
+
+def _pack_geometry(geom, row, coeffs: list, forbes: bool = False, grating: bool = False,
+                   grid_sag: bool = False):
     name = type(geom).__name__
     row["coeff_offset"] = len(coeffs)
     row["n_coeff"] = 0
@@ -368,6 +421,9 @@ def _pack_geometry(geom, row, coeffs: list, forbes: bool = False, grating: bool 
     row["norm_radius"] = 1.0
     if grating:   # (the caller saw the classes: `_is_grating`)
         _pack_grating(geom, row, coeffs)
+        return
+    if grid_sag:   # (the caller saw the class: `_is_grid_sag`)
+        _pack_grid_sag(geom, row, coeffs)
         return
     if name == "Plane":
         row["geom_kind"] = S.GEOM_PLANE
@@ -591,13 +647,18 @@ def _is_phase_row(row) -> bool:
     return int(row["geom_kind"]) == S.GEOM_PLANE_PHASE
 
 
+def _is_grid_sag_row(row) -> bool:
+    return int(row["geom_kind"]) == S.GEOM_GRID_SAG
+
+
 def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, gratings: bool = False,
-                        phases: bool = False):
+                        phases: bool = False, grid_sags: bool = False):
     """One surface, packed by itself: (desc row, its coefficient block as a list with every
     offset RELATIVE to the block, optics rows per wavelength).  Raises `UnsupportedSystem`.
     forbes: a Forbes surface is packed as a row of its own kind (`pack_surfaces(tolerate=True)`)
     instead of raising; gratings: so is a diffraction grating (`pack_surfaces(tolerate=True,
-    gratings=True)`); phases: and so is a phase-profile plane (`phases=True`)."""
+    gratings=True)`); phases: and so is a phase-profile plane (`phases=True`); grid_sags: and a
+    grid-sag surface (`grid_sags=True`)."""
     row = np.zeros((), dtype=S.SURFACE_DESC_DTYPE)
     opt = np.zeros(wl.size, dtype=S.SURFACE_OPTICS_DTYPE)
     coeffs: list = []
@@ -617,12 +678,14 @@ def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, grating
         )
     if getattr(im, "bsdf", None) is not None:
         raise UnsupportedSystem("BSDF scatter is not on the fused path")
-    _pack_geometry(geom, row, coeffs, forbes and not is_object, grating)
+    grid_sag = grid_sags and not is_object and _is_grid_sag(surf)
+    _pack_geometry(geom, row, coeffs, forbes and not is_object, grating, grid_sag)
     if phase:   # (the geometry is a Plane: `_is_phase`)
         _pack_phase(surf, wl, row, coeffs)
     if S.OPTIONS["reference_newton"] and int(row["geom_kind"]) not in (S.GEOM_PLANE,
                                                                       S.GEOM_STANDARD,
-                                                                      S.GEOM_PLANE_PHASE):
+                                                                      S.GEOM_PLANE_PHASE,
+                                                                      S.GEOM_GRID_SAG):
         # the reference's batch-global stop rule on this Newton-Raphson surface (opt-in)
         row["flags"] |= S.SURF_REFERENCE_NEWTON
     _pack_aperture(surf.aperture, row, coeffs)
@@ -633,6 +696,8 @@ def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, grating
         raise UnsupportedSystem("polarisation-dependent coating on a grating")
     if phase and int(row["coating_kind"]) >= S.COAT_FRESNEL:
         raise UnsupportedSystem("polarisation-dependent coating on a phase surface")
+    if grid_sag and int(row["coating_kind"]) >= S.COAT_FRESNEL:
+        raise UnsupportedSystem("polarisation-dependent coating on a grid-sag surface")
     if is_object:
         # ObjectSurface.trace only records (surfaces/object_surface.py:56-93)
         row["interaction"] = S.INTERACT_RECORD_ONLY
@@ -694,7 +759,8 @@ def _relocate(row, local: list, base: int):
 
 def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
                   tolerate: bool = False, tokens=None, cache: dict | None = None,
-                  keep=None, gratings: bool = False, phases: bool = False) -> SystemTable:
+                  keep=None, gratings: bool = False, phases: bool = False,
+                  grid_sags: bool = False) -> SystemTable:
     """Flatten a sequence of reference `Surface` objects (a `SurfaceGroup`'s list) for
     the given wavelengths (microns): everything `SurfaceGroup.trace`
     (surfaces/surface_group.py:245-257) needs -- no ray-generator scalars, no
@@ -717,7 +783,9 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
     PhaseInteractionModel (`_is_phase`; `HipSystem.can_trace_phase`): packed and listed in
     `table.phases` with `tolerate` AND `phases`, in `table.unsupported` without, and also when
     the kernel does not serve it (`_pack_phase`, a BSDF, a Jones coating, an inhomogeneous
-    medium).
+    medium).  `grid_sags` does the same for the reference's GridSagGeometry (`_is_grid_sag`, an
+    exact class match; `HipSystem.can_trace_grid_sag`): `table.grid_sag_rows`, or
+    `table.unsupported` (`_pack_grid_sag`, a BSDF, a Jones coating, an inhomogeneous medium).
 
     `tokens` + `cache` (both or neither): per-surface change-detector tokens
     (fingerprint.surface_token, i.e. element [1] of `optic_token`) and a dict the caller
@@ -777,11 +845,17 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
                     if not tolerate:
                         raise UnsupportedSystem("a phase surface is not on the fused path")
                     packed = None   # (cached by a pack that served phase surfaces)
+                if packed is not None and _is_grid_sag_row(packed[0]) \
+                        and not (tolerate and grid_sags):
+                    if not tolerate:
+                        raise UnsupportedSystem("a grid-sag surface is not on the fused path")
+                    packed = None   # (cached by a pack that served grid-sag surfaces)
         if packed is None:
             try:
                 packed = _pack_surface_local(i == 0, surf, wl, forbes=tolerate,
                                              gratings=tolerate and gratings,
-                                             phases=tolerate and phases)
+                                             phases=tolerate and phases,
+                                             grid_sags=tolerate and grid_sags)
             except UnsupportedSystem:
                 if not tolerate or i == 0:
                     raise
@@ -811,7 +885,7 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
     table.last_thickness = _f(surfaces[-1].thickness) if n_s else 0.0
     table.unsupported = tuple(unsupported)
     if use_cache and not unsupported and not table.forbes and not table.gratings \
-            and not table.phases:
+            and not table.phases and not table.grid_sag_rows:
         cache["assembled"] = (tuple(id(s_) for s_ in surfaces), wl_key, list(tokens), bases,
                               table)
     return table

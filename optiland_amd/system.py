@@ -33,6 +33,8 @@ GEOM_PLANE_GRATING, GEOM_STANDARD_GRATING = 11, 12
 # of ol_geom_kind in include/optiland_hip.h has the layout
 GEOM_PLANE_PHASE = 14   # (13 is no kind: the library refuses it as unknown, as it always did)
 PHASE_CONSTANT, PHASE_LINEAR, PHASE_RADIAL, PHASE_GRID = 0, 1, 2, 3
+# a grid of sag values likewise (ol_trace_grid_sag); block: {W, H, W x, H y, H * W sags}
+GEOM_GRID_SAG = 16   # (15 and 17 are no kinds: the library refuses them as unknown, as always)
 INTERACT_RECORD_ONLY, INTERACT_REFRACT, INTERACT_REFLECT = 0, 1, 2
 AP_NONE, AP_RADIAL, AP_OFFSET_RADIAL, AP_RECTANGULAR, AP_ELLIPTICAL = 0, 1, 2, 3, 4
 AP_COMPOSITE = 5
@@ -80,6 +82,7 @@ GEOM_NAMES = {
     GEOM_PLANE_GRATING: "plane_grating",
     GEOM_STANDARD_GRATING: "standard_grating",
     GEOM_PLANE_PHASE: "plane_phase",
+    GEOM_GRID_SAG: "grid_sag",
 }
 
 # numpy image of `ol_surface_desc`; align=True reproduces the C layout.
@@ -228,6 +231,17 @@ class SystemTable:
                 int(i) for i in np.nonzero(g == GEOM_PLANE_PHASE)[0])
         return memo
 
+    @property
+    def grid_sag_rows(self) -> tuple:
+        """Indices of the grid-sag rows (GEOM_GRID_SAG): each is one `ol_trace_grid_sag` launch
+        between two fused runs, like the Forbes rows."""
+        memo = self.__dict__.get("_grid_sag_rows")
+        if memo is None:
+            g = self.surfaces["geom_kind"]
+            memo = self.__dict__["_grid_sag_rows"] = tuple(
+                int(i) for i in np.nonzero(g == GEOM_GRID_SAG)[0])
+        return memo
+
     def reference_newton_surfaces(self, first: int = 0, last: int | None = None) -> list:
         """Traced Newton-Raphson surfaces of [first, last] that carry SURF_REFERENCE_NEWTON (the
         reference's batch-global stop rule, newton_raphson.py:137-166): their iteration count is
@@ -242,6 +256,7 @@ class SystemTable:
                                            & (s["geom_kind"] != GEOM_PLANE_GRATING)
                                            & (s["geom_kind"] != GEOM_STANDARD_GRATING)
                                            & (s["geom_kind"] != GEOM_PLANE_PHASE)
+                                           & (s["geom_kind"] != GEOM_GRID_SAG)
                                            & (s["interaction"] != INTERACT_RECORD_ONLY))[0]]
         if not memo:
             return memo

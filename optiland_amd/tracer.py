@@ -43,6 +43,8 @@ def _make_engine(table: SystemTable, device):
 _make_engine.traces_gratings = True
 # ... and likewise for phase-profile planes (`pack_surfaces(phases=True)`, `table.phases`)
 _make_engine.traces_phases = True
+# ... and for grid-sag surfaces (`pack_surfaces(grid_sags=True)`, `table.grid_sag_rows`)
+_make_engine.traces_grid_sags = True
 
 
 class RecordedSurfaces:
