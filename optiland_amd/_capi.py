@@ -13,6 +13,7 @@ from . import build as _build
 from .system import GEOM_PLANE_GRATING, GEOM_STANDARD_GRATING  # noqa: F401 - OL_GEOM_*_GRATING
 from .system import GEOM_PLANE_PHASE  # noqa: F401 - OL_GEOM_PLANE_PHASE
 from .system import GEOM_GRID_SAG  # noqa: F401 - OL_GEOM_GRID_SAG
+from .system import SINGLE_KINDS
 
 _LIB = None
 
@@ -312,22 +313,12 @@ def bind(lib, path: str = "?"):
         lib.ol_aim_rays.restype = C.c_int
         lib.ol_aim_rays.argtypes = [vp, i64, i32, i32, i32, vp, vp, C.POINTER(vp), C.POINTER(vp),
                                     vp, vp, vp]
-    if has_trace_forbes(lib):   # (additive within ABI 11, like ol_huygens_psf)
-        lib.ol_trace_forbes.restype = C.c_int
-        lib.ol_trace_forbes.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, vp, i64, i32, u32,
-                                        vp, vp]
-    if has_trace_grating(lib):   # (additive within ABI 11, like ol_huygens_psf)
-        lib.ol_trace_grating.restype = C.c_int
-        lib.ol_trace_grating.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, C.c_double, vp, i64,
-                                         i32, u32, vp, vp]
-    if has_trace_phase(lib):   # (additive within ABI 11, like ol_trace_grating)
-        lib.ol_trace_phase.restype = C.c_int
-        lib.ol_trace_phase.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, C.c_double, vp, i64,
-                                       i32, u32, vp, vp]
-    if has_trace_grid_sag(lib):   # (additive within ABI 11, like ol_trace_forbes)
-        lib.ol_trace_grid_sag.restype = C.c_int
-        lib.ol_trace_grid_sag.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32, vp, i64, i32, u32,
-                                          vp, vp]
+    for kind in SINGLE_KINDS:   # (each additive within ABI 11, like ol_huygens_psf)
+        entry = getattr(lib, "ol_trace_" + kind.name, None)
+        if entry is not None:
+            entry.restype = C.c_int
+            entry.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32] \
+                + ([C.c_double] if kind.wavelength else []) + [vp, i64, i32, u32, vp, vp]
     return lib
 
 

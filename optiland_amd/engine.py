@@ -11,6 +11,7 @@ import ctypes as C
 import logging
 import threading
 import os
+import sys
 import time
 import weakref
 
@@ -452,19 +453,25 @@ def _start_sweeper() -> None:
     t.start()
 
 
-def split_trace(forbes, first: int, last: int, rec, rec_first: int, fused, one) -> None:
-    """Walk surfaces [first, last] as fused runs and single Forbes launches, in order.
+# `ol_trace_<name>` and `trace_<name>` of every single-launch kind (interned: `getattr` with a
+# name put together at call time misses the type's method cache, ~0.4 us a look-up)
+_SINGLE_ENTRY = {k: sys.intern("ol_trace_" + k.name) for k in S.SINGLE_KINDS}
+_SINGLE_METHOD = {k: sys.intern("trace_" + k.name) for k in S.SINGLE_KINDS}
 
-    forbes: the table's single-launch rows -- `SystemTable.forbes` and, with them,
-    `SystemTable.gratings` and `SystemTable.phases`: the caller passes the union and tells them
-    apart in `one` (the parameter keeps its name: callers pass it by position or by this name).  rec: the caller's
-    record block or None; its row 0 holds surface `rec_first`.  `fused(a, b, rec_view, rec_from, midrange)` traces
-    the run [a, b] -- `rec_view` is the part of the block whose row 0 is surface `rec_from`, or
-    None when the run lies in front of the first recorded surface; `one(s, row, midrange)` traces
-    the Forbes surface s (`row`: its (8, stride) row of the block, or None).  Both carry the ray
-    state in the SAME eight planes (written back after every launch); `midrange`: the trace goes
-    on behind this launch.  One splitter for stand-alone callers and for the drop-in's bridge."""
-    cut = set(forbes)
+
+def split_trace(rows, first: int, last: int, rec, rec_first: int, fused, one) -> None:
+    """Walk surfaces [first, last] as fused runs and single-surface launches, in order.
+
+    rows: the table's single-launch rows (`SystemTable.singles`, or the rows of one kind where a
+    table has no other): the caller tells their kinds apart in `one`.  rec: the caller's
+    record block or None; its row 0 holds surface `rec_first`.  `fused(a, b, rec_view, rec_from,
+    midrange)` traces the run [a, b] -- `rec_view` is the part of the block whose row 0 is
+    surface `rec_from`, or None when the run lies in front of the first recorded surface;
+    `one(s, row, midrange)` traces the single-launch surface s (`row`: its (8, stride) row of the
+    block, or None).  Both carry the ray state in the SAME eight planes (written back after every
+    launch); `midrange`: the trace goes on behind this launch.  One splitter for stand-alone
+    callers and for the drop-in's bridge."""
+    cut = set(rows)
     s = first
     while s <= last:
         if s in cut:
@@ -858,8 +865,7 @@ class HipSystem:
                 raise ValueError("record must be a contiguous (rows, 8, stride>=n) tensor")
         if write_rays is None:
             write_rays = rec is None
-        singles = self.table.forbes + self.table.gratings + self.table.phases \
-            + self.table.grid_sag_rows
+        singles = self.table.singles
         if singles and any(first <= f <= last for f in singles):
             if prt is not None or spot is not None:
                 raise ValueError("a range with Forbes surfaces, gratings, phase surfaces or "
@@ -941,12 +947,8 @@ class HipSystem:
         recorded): the state is written back into `rays`.  midrange: the caller traces on behind
         this surface (the informational STATUS_NAN_DIRECTION is then not raised here).  Returns
         the status word (0 when deferred or unchecked).  A missing kernel is an error."""
-        if not self.can_trace_forbes():
-            raise _capi.HipExtensionError("the loaded library has no ol_trace_forbes: rebuild it")
-        return self._trace_single("ol_trace_forbes", (), self.table.forbes, "a Forbes", rays,
-                                  surface, wavelength_index,
-                                  record_row, write_rays, midrange, check_status, defer_status,
-                                  zero_status)
+        return self._trace_single(S.KIND_FORBES, rays, surface, wavelength_index, record_row,
+                                  write_rays, midrange, check_status, defer_status, zero_status)
 
     # ---- diffraction gratings (ol_trace_grating: one surface, one launch) ---------------------
     def can_trace_grating(self) -> bool:
@@ -961,13 +963,8 @@ class HipSystem:
         `table.wavelengths[wavelength_index]`, back to the global frame.  An evanescent order
         leaves a finite position and a NaN direction (STATUS_NAN_DIRECTION unless midrange).  A
         missing kernel is an error."""
-        if not self.can_trace_grating():
-            raise _capi.HipExtensionError("the loaded library has no ol_trace_grating: rebuild it")
-        wl = float(self.table.wavelengths[int(wavelength_index)])
-        return self._trace_single("ol_trace_grating", (wl,), self.table.gratings, "a grating",
-                                  rays, surface, wavelength_index,
-                                  record_row, write_rays, midrange, check_status, defer_status,
-                                  zero_status)
+        return self._trace_single(S.KIND_GRATING, rays, surface, wavelength_index, record_row,
+                                  write_rays, midrange, check_status, defer_status, zero_status)
 
     # ---- phase-profile planes (ol_trace_phase: one surface, one launch) ------------------------
     def can_trace_phase(self) -> bool:
@@ -982,13 +979,8 @@ class HipSystem:
         at the wavelength `table.wavelengths[wavelength_index]`, the phase taken off the optical
         path, back to the global frame.  An evanescent ray leaves intensity 0, a finite direction
         and no status bit, as in the reference.  A missing kernel is an error."""
-        if not self.can_trace_phase():
-            raise _capi.HipExtensionError("the loaded library has no ol_trace_phase: rebuild it")
-        wl = float(self.table.wavelengths[int(wavelength_index)])
-        return self._trace_single("ol_trace_phase", (wl,), self.table.phases, "a phase", rays,
-                                  surface, wavelength_index,
-                                  record_row, write_rays, midrange, check_status, defer_status,
-                                  zero_status)
+        return self._trace_single(S.KIND_PHASE, rays, surface, wavelength_index, record_row,
+                                  write_rays, midrange, check_status, defer_status, zero_status)
 
     # ---- grid-sag surfaces (ol_trace_grid_sag: one surface, one launch) ------------------------
     def can_trace_grid_sag(self) -> bool:
@@ -1003,18 +995,20 @@ class HipSystem:
         stopped per ray, interaction, back to the global frame.  A ray that leaves the grid comes
         out with NaN position and direction (STATUS_NAN_DIRECTION unless midrange), as in the
         reference.  A missing kernel is an error."""
-        if not self.can_trace_grid_sag():
-            raise _capi.HipExtensionError("the loaded library has no ol_trace_grid_sag: rebuild it")
-        return self._trace_single("ol_trace_grid_sag", (), self.table.grid_sag_rows, "a grid-sag",
-                                  rays, surface, wavelength_index,
-                                  record_row, write_rays, midrange, check_status, defer_status,
-                                  zero_status)
+        return self._trace_single(S.KIND_GRID_SAG, rays, surface, wavelength_index, record_row,
+                                  write_rays, midrange, check_status, defer_status, zero_status)
 
-    def _trace_single(self, entry, extra, rows, kind, rays, surface, wavelength_index, record_row,
-                      write_rays, midrange, check_status, defer_status, zero_status) -> int:
-        """The launch `trace_forbes`, `trace_grating`, `trace_phase` and `trace_grid_sag` share:
-        `entry` takes `extra` behind the wavelength index and serves the table's `rows` ("`kind`
-        row"), everything else alike -- the checks in the order `trace_forbes` always made them."""
+    def _trace_single(self, kind, rays, surface, wavelength_index, record_row, write_rays,
+                      midrange, check_status, defer_status, zero_status) -> int:
+        """The launch `trace_forbes`, `trace_grating`, `trace_phase` and `trace_grid_sag` share
+        (`kind`: the `system.SingleKind` of the caller): `ol_trace_<name>` serves the table's rows
+        of that kind and, for some kinds, takes the wavelength behind its index; everything else
+        alike -- the checks in the order `trace_forbes` always made them."""
+        entry = _SINGLE_ENTRY[kind]
+        launch = getattr(self.lib, entry, None)   # (what `can_trace_<name>` asks)
+        if launch is None:
+            raise _capi.HipExtensionError(f"the loaded library has no {entry}: rebuild it")
+        extra = (float(self.table.wavelengths[int(wavelength_index)]),) if kind.wavelength else ()
         rays = list(rays)
         if len(rays) != 8:
             raise ValueError("rays must be 8 planes: x,y,z,L,M,N,i,opd")
@@ -1025,8 +1019,8 @@ class HipSystem:
         for t in rays:
             if t.device != self.device or t.dtype != dtype or t.numel() != n or not t.is_contiguous():
                 raise ValueError("ray planes must be contiguous, same dtype/size, on the system's device")
-        if int(surface) not in rows:
-            raise ValueError(f"surface {surface} is not {kind} row of this table")
+        if self.table.single_rows.get(int(surface)) is not kind:
+            raise ValueError(f"surface {surface} is not {kind.row_noun} row of this table")
         row = record_row
         if row is not None:
             if row.dtype != dtype or row.dim() != 2 or row.shape[0] != 8 or row.shape[1] < n \
@@ -1041,7 +1035,7 @@ class HipSystem:
         if check_status and zero_status:
             self._status.zero_()
         with self._device_ctx():
-            rc = getattr(self.lib, entry)(
+            rc = launch(
                 self._handle, _DT[dtype], n, ptrs, int(wavelength_index), *extra,
                 row.data_ptr() if row is not None else None,
                 int(row.shape[1]) if row is not None else 0, int(surface), flags,
@@ -1053,7 +1047,7 @@ class HipSystem:
 
     def _trace_split(self, rays, wl, rec, rec_first, first, last, write_rays, check_status,
                      defer_status, zero_status) -> TraceResult:
-        """`trace` over a range with Forbes, grating or phase rows (`split_trace`).  The state travels in
+        """`trace` over a range with single-launch rows (`split_trace`).  The state travels in
         `rays` themselves (write_rays) or in a private copy of them; every launch ORs into the one
         status word, except that what a fused run in FRONT of a later launch reports about its
         own last surface (STATUS_NAN_DIRECTION) is dropped: it is not the end of this trace."""
@@ -1074,18 +1068,14 @@ class HipSystem:
                        zero_status=False, record_first=r0 if (r0 is not None and r0 != a) else None,
                        _status_to=word)
 
-        gratings, phases = set(self.table.gratings), set(self.table.phases)
-        grid_sags = set(self.table.grid_sag_rows)
+        kinds = self.table.single_rows
 
         def one(s, row, midrange):
-            launch = self.trace_grating if s in gratings else \
-                self.trace_phase if s in phases else \
-                self.trace_grid_sag if s in grid_sags else self.trace_forbes
-            launch(work, s, wl, record_row=row, write_rays=True, midrange=midrange,
-                   check_status=check_status, defer_status=True, zero_status=False)
+            getattr(self, _SINGLE_METHOD[kinds[s]])(
+                work, s, wl, record_row=row, write_rays=True, midrange=midrange,
+                check_status=check_status, defer_status=True, zero_status=False)
 
-        split_trace(self.table.forbes + self.table.gratings + self.table.phases
-                    + self.table.grid_sag_rows, first, last, rec, rec_first, fused, one)
+        split_trace(self.table.singles, first, last, rec, rec_first, fused, one)
         if mid:
             self._status.bitwise_or_(mid[0].bitwise_and_(~S.STATUS_NAN_DIRECTION))
         status = int(self._status.item()) if (check_status and not defer_status) else 0

@@ -33,6 +33,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import os
+import sys
 
 import numpy as np
 import torch
@@ -956,13 +957,14 @@ def _make_tracer_class():
 # --------------------------------------------------------------------------------------
 # SurfaceGroup.trace(rays, skip) -- the seam for callers that bring their own rays
 # --------------------------------------------------------------------------------------
-_SG = {"device": None, "force": False, "count": 0, "fallbacks": 0, "foreign": 0,
-       # enable(gratings=...): diffraction gratings as device work (OPTILAND_HIP_GRATINGS=0: off)
-       "gratings": os.environ.get("OPTILAND_HIP_GRATINGS", "1") != "0",
-       # enable(phases=...): phase-profile planes likewise (OPTILAND_HIP_PHASES=0: off)
-       "phases": os.environ.get("OPTILAND_HIP_PHASES", "1") != "0",
-       # enable(grid_sags=...): grid-sag surfaces likewise (OPTILAND_HIP_GRID_SAGS=0: off)
-       "grid_sags": os.environ.get("OPTILAND_HIP_GRID_SAGS", "1") != "0"}
+_SG = {"device": None, "force": False, "count": 0, "fallbacks": 0, "foreign": 0}
+# switch -> the engine factory's `traces_<switch>` (interned: `getattr` with a name put together
+# at call time misses the type's method cache)
+_SWITCHES = {k.switch: sys.intern("traces_" + k.switch) for k in _S.SINGLE_KINDS
+             if k.switch is not None}
+# enable(gratings=..., phases=..., grid_sags=...): those kinds of surface as device work
+# (OPTILAND_HIP_GRATINGS=0, OPTILAND_HIP_PHASES=0, OPTILAND_HIP_GRID_SAGS=0: seeded off)
+_SG.update((sw, os.environ.get("OPTILAND_HIP_" + sw.upper(), "1") != "0") for sw in _SWITCHES)
 # settings of the class-wide patch (enable())
 _ENABLE = {"device": None, "force": False, "lazy": False}
 _PLANE_ATTRS = ("x", "y", "z", "L", "M", "N", "i", "opd")
@@ -1006,34 +1008,29 @@ def _sg_table(group, wavelength):
     after bundle through an unchanged SurfaceGroup packs it once.  None = the fused path
     refuses the whole group.
 
-    Grating rows are packed as such (`table.gratings`) only when the engine factory in use
-    declares that its engines trace them (`tracer._make_engine.traces_gratings`) and
-    `enable(gratings=False)` / OPTILAND_HIP_GRATINGS=0 has not switched them off: decided HERE,
-    before packing, so that the production path packs once and a stand-in factory that knows
-    nothing of gratings gets the table -- and the reference's own surface -- it always got.
-    Phase-profile planes (`table.phases`) likewise: `traces_phases`, `enable(phases=False)` /
-    OPTILAND_HIP_PHASES=0.  Grid-sag surfaces (`table.grid_sag_rows`) likewise:
-    `traces_grid_sags`, `enable(grid_sags=False)` / OPTILAND_HIP_GRID_SAGS=0."""
-    gratings = bool(_SG["gratings"]) and bool(getattr(_tracer._make_engine, "traces_gratings",
-                                                      False))
-    phases = bool(_SG["phases"]) and bool(getattr(_tracer._make_engine, "traces_phases", False))
-    grid_sags = bool(_SG["grid_sags"]) and bool(getattr(_tracer._make_engine, "traces_grid_sags",
-                                                        False))
+    The rows of a switched single-launch kind (`system.SINGLE_KINDS`: gratings, phase-profile
+    planes, grid-sag surfaces) are packed as such only when the engine factory in use declares
+    that its engines trace them (`tracer._make_engine.traces_<switch>`) and `enable(<switch>=
+    False)` / OPTILAND_HIP_<SWITCH>=0 has not switched them off: decided HERE, before packing,
+    so that the production path packs once and a stand-in factory that knows nothing of a kind
+    gets the table -- and the reference's own surface -- it always got."""
+    served = tuple(sw for sw, declares in _SWITCHES.items()
+                   if _SG[sw] and getattr(_tracer._make_engine, declares, False))
     tok = None
     if _fp.ENABLED:
         tok, _keep = _fp.surfaces_token(group.surfaces, wavelength)
         memo = group.__dict__.get("_hip_sg_memo")
         memo = memo.value if memo is not None else None
-        if memo is not None and memo[0] == tok and memo[3] == (gratings, phases, grid_sags):
+        if memo is not None and memo[0] == tok and memo[3] == served:
             return memo[2]
     try:
         table = pack_surfaces(group.surfaces, [wavelength], name="SurfaceGroup", tolerate=True,
-                              gratings=gratings, phases=phases, grid_sags=grid_sags)
+                              **dict.fromkeys(served, True))
     except UnsupportedSystem:
         table = None
     if tok is not None:
         tok, keep = _fp.surfaces_token(group.surfaces, wavelength)  # after the pack
-        group.__dict__["_hip_sg_memo"] = _Volatile((tok, keep, table, (gratings, phases, grid_sags)))
+        group.__dict__["_hip_sg_memo"] = _Volatile((tok, keep, table, served))
     return table
 
 
@@ -1182,8 +1179,7 @@ def _hip_surface_group_trace(group, rays, skip):
         return None
     foreign = set(table.unsupported)
     if polarized:
-        foreign |= set(table.forbes) | set(table.gratings) | set(table.phases) \
-            | set(table.grid_sag_rows)
+        foreign |= set(table.singles)
     if len(foreign) >= n_s - skip - (1 if skip == 0 else 0):
         return None  # nothing but the object row would run fused
     if table.uses_polarization and not polarized:
@@ -1426,12 +1422,9 @@ def enable(device=None, force=False, analyses=True, lazy_records=False, placed_r
     _set_record_pool(placed_records)
     _set_reference_root(reference_root)
     _set_reference_newton(reference_newton)
-    if gratings is not None:
-        _SG["gratings"] = bool(gratings)
-    if phases is not None:
-        _SG["phases"] = bool(phases)
-    if grid_sags is not None:
-        _SG["grid_sags"] = bool(grid_sags)
+    for switch, value in (("gratings", gratings), ("phases", phases), ("grid_sags", grid_sags)):
+        if value is not None:
+            _SG[switch] = bool(value)
     cls = _make_tracer_class()
     from optiland.raytrace.real_ray_tracer import RealRayTracer
 

@@ -409,8 +409,21 @@ def _pack_grid_sag(geom, row, coeffs: list) -> None:
     coeffs.extend(block)
 
 
-def _pack_geometry(geom, row, coeffs: list, forbes: bool = False, grating: bool = False,
-                   grid_sag: bool = False):
+# the kinds that are recognised before the geometry is looked at, in the order they are tried
+# (Forbes surfaces are the last resort of `_pack_geometry`)
+_RECOGNISERS = ((S.KIND_GRATING, _is_grating), (S.KIND_PHASE, _is_phase),
+                (S.KIND_GRID_SAG, _is_grid_sag))
+
+
+def _single_kind(surf, served):
+    """The kind among `served` whose recogniser takes `surf`, or None."""
+    for kind, recognise in _RECOGNISERS:
+        if kind in served and recognise(surf):
+            return kind
+    return None
+
+
+def _pack_geometry(geom, row, coeffs: list, served=frozenset(), kind=None):
     name = type(geom).__name__
     row["coeff_offset"] = len(coeffs)
     row["n_coeff"] = 0
@@ -419,10 +432,10 @@ def _pack_geometry(geom, row, coeffs: list, forbes: bool = False, grating: bool 
     row["tol"] = 0.0
     row["max_iter"] = 0
     row["norm_radius"] = 1.0
-    if grating:   # (the caller saw the classes: `_is_grating`)
+    if kind is S.KIND_GRATING:   # (the caller saw the classes: `_is_grating`)
         _pack_grating(geom, row, coeffs)
         return
-    if grid_sag:   # (the caller saw the class: `_is_grid_sag`)
+    if kind is S.KIND_GRID_SAG:   # (the caller saw the class: `_is_grid_sag`)
         _pack_grid_sag(geom, row, coeffs)
         return
     if name == "Plane":
@@ -504,7 +517,7 @@ def _pack_geometry(geom, row, coeffs: list, forbes: bool = False, grating: bool 
         for c, (n, m) in zip(cj, z.indices):
             coeffs.extend([float(c), float(n), float(m), _f(z._norm_constant(n, m))])
         return
-    if forbes:
+    if S.KIND_FORBES in served:
         classes = _forbes_classes()
         if classes is not None and isinstance(geom, classes):
             _pack_forbes(geom, row, coeffs, classes)
@@ -635,30 +648,12 @@ def _scalar_index(material, w: float, which: str) -> float:
     return hit
 
 
-def _is_forbes_row(row) -> bool:
-    return int(row["geom_kind"]) in (S.GEOM_FORBES_Q, S.GEOM_FORBES_Q2D)
-
-
-def _is_grating_row(row) -> bool:
-    return int(row["geom_kind"]) in (S.GEOM_PLANE_GRATING, S.GEOM_STANDARD_GRATING)
-
-
-def _is_phase_row(row) -> bool:
-    return int(row["geom_kind"]) == S.GEOM_PLANE_PHASE
-
-
-def _is_grid_sag_row(row) -> bool:
-    return int(row["geom_kind"]) == S.GEOM_GRID_SAG
-
-
-def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, gratings: bool = False,
-                        phases: bool = False, grid_sags: bool = False):
+def _pack_surface_local(is_object: bool, surf, wl, served=frozenset()):
     """One surface, packed by itself: (desc row, its coefficient block as a list with every
     offset RELATIVE to the block, optics rows per wavelength).  Raises `UnsupportedSystem`.
-    forbes: a Forbes surface is packed as a row of its own kind (`pack_surfaces(tolerate=True)`)
-    instead of raising; gratings: so is a diffraction grating (`pack_surfaces(tolerate=True,
-    gratings=True)`); phases: and so is a phase-profile plane (`phases=True`); grid_sags: and a
-    grid-sag surface (`grid_sags=True`)."""
+    served: the `system.SINGLE_KINDS` that are packed as rows of their own kind instead of raising
+    (`pack_surfaces`: Forbes surfaces with `tolerate`, the others with their switch as well); the
+    object surface is never one."""
     row = np.zeros((), dtype=S.SURFACE_DESC_DTYPE)
     opt = np.zeros(wl.size, dtype=S.SURFACE_OPTICS_DTYPE)
     coeffs: list = []
@@ -670,17 +665,17 @@ def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, grating
     if S.OPTIONS["reference_root"]:   # (the C side honours it on curved standard surfaces only)
         row["flags"] |= S.SURF_REFERENCE_ROOT
     im = surf.interaction_model
-    grating = gratings and not is_object and _is_grating(surf)
-    phase = phases and not is_object and _is_phase(surf)
-    if type(im).__name__ != "RefractiveReflectiveModel" and not grating and not phase:
+    if is_object:
+        served = frozenset()
+    kind = _single_kind(surf, served)
+    if type(im).__name__ != "RefractiveReflectiveModel" and kind is None:
         raise UnsupportedSystem(
             f"interaction model {type(im).__name__} is not on the fused path"
         )
     if getattr(im, "bsdf", None) is not None:
         raise UnsupportedSystem("BSDF scatter is not on the fused path")
-    grid_sag = grid_sags and not is_object and _is_grid_sag(surf)
-    _pack_geometry(geom, row, coeffs, forbes and not is_object, grating, grid_sag)
-    if phase:   # (the geometry is a Plane: `_is_phase`)
+    _pack_geometry(geom, row, coeffs, served, kind)
+    if kind is S.KIND_PHASE:   # (the geometry is a Plane: `_is_phase`)
         _pack_phase(surf, wl, row, coeffs)
     if S.OPTIONS["reference_newton"] and int(row["geom_kind"]) not in (S.GEOM_PLANE,
                                                                       S.GEOM_STANDARD,
@@ -690,14 +685,9 @@ def _pack_surface_local(is_object: bool, surf, wl, forbes: bool = False, grating
         row["flags"] |= S.SURF_REFERENCE_NEWTON
     _pack_aperture(surf.aperture, row, coeffs)
     _pack_coating(surf.coating, row, coeffs)
-    if _is_forbes_row(row) and int(row["coating_kind"]) >= S.COAT_FRESNEL:
-        raise UnsupportedSystem("polarisation-dependent coating on a Forbes surface")
-    if grating and int(row["coating_kind"]) >= S.COAT_FRESNEL:
-        raise UnsupportedSystem("polarisation-dependent coating on a grating")
-    if phase and int(row["coating_kind"]) >= S.COAT_FRESNEL:
-        raise UnsupportedSystem("polarisation-dependent coating on a phase surface")
-    if grid_sag and int(row["coating_kind"]) >= S.COAT_FRESNEL:
-        raise UnsupportedSystem("polarisation-dependent coating on a grid-sag surface")
+    kind = S.KIND_OF_GEOM.get(int(row["geom_kind"]))   # (a Forbes row is known by now as well)
+    if kind is not None and int(row["coating_kind"]) >= S.COAT_FRESNEL:
+        raise UnsupportedSystem(f"polarisation-dependent coating on {kind.noun}")
     if is_object:
         # ObjectSurface.trace only records (surfaces/object_surface.py:56-93)
         row["interaction"] = S.INTERACT_RECORD_ONLY
@@ -806,6 +796,9 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
         + (b"|reference_newton" if S.OPTIONS["reference_newton"] else b"")
     n_s = len(surfaces)
     use_cache = cache is not None and tokens is not None and len(tokens) == n_s
+    switches = {"gratings": gratings, "phases": phases, "grid_sags": grid_sags}
+    served = frozenset(k for k in S.SINGLE_KINDS
+                       if tolerate and (k.switch is None or switches[k.switch]))
     if use_cache:
         # rows of surfaces that left the optic go (their ids are free to be recycled); what
         # stays is pinned: the surfaces themselves and everything the current tokens name
@@ -835,27 +828,14 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
             hit = cache.get(id(surf))
             if hit is not None and hit[0] == (tokens[i], i == 0, wl_key):
                 packed = hit[1]
-                if not tolerate and _is_forbes_row(packed[0]):   # (cached by a tolerant pack)
-                    raise UnsupportedSystem("Forbes geometry is not on the fused path")
-                if _is_grating_row(packed[0]) and not (tolerate and gratings):
+                kind = S.KIND_OF_GEOM.get(int(packed[0]["geom_kind"]))
+                if kind is not None and kind not in served:   # (cached by a pack that served it)
                     if not tolerate:
-                        raise UnsupportedSystem("a grating is not on the fused path")
-                    packed = None   # (cached by a pack that served gratings: decided below)
-                if packed is not None and _is_phase_row(packed[0]) and not (tolerate and phases):
-                    if not tolerate:
-                        raise UnsupportedSystem("a phase surface is not on the fused path")
-                    packed = None   # (cached by a pack that served phase surfaces)
-                if packed is not None and _is_grid_sag_row(packed[0]) \
-                        and not (tolerate and grid_sags):
-                    if not tolerate:
-                        raise UnsupportedSystem("a grid-sag surface is not on the fused path")
-                    packed = None   # (cached by a pack that served grid-sag surfaces)
+                        raise UnsupportedSystem(f"{kind.unserved} is not on the fused path")
+                    packed = None   # (decided below)
         if packed is None:
             try:
-                packed = _pack_surface_local(i == 0, surf, wl, forbes=tolerate,
-                                             gratings=tolerate and gratings,
-                                             phases=tolerate and phases,
-                                             grid_sags=tolerate and grid_sags)
+                packed = _pack_surface_local(i == 0, surf, wl, served)
             except UnsupportedSystem:
                 if not tolerate or i == 0:
                     raise
@@ -884,8 +864,7 @@ def pack_surfaces(surfaces, wavelengths, name: str = "surfaces",
     )
     table.last_thickness = _f(surfaces[-1].thickness) if n_s else 0.0
     table.unsupported = tuple(unsupported)
-    if use_cache and not unsupported and not table.forbes and not table.gratings \
-            and not table.phases and not table.grid_sag_rows:
+    if use_cache and not unsupported and not table.singles:
         cache["assembled"] = (tuple(id(s_) for s_ in surfaces), wl_key, list(tokens), bases,
                               table)
     return table

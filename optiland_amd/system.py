@@ -85,6 +85,34 @@ GEOM_NAMES = {
     GEOM_GRID_SAG: "grid_sag",
 }
 
+
+@dataclass(frozen=True, eq=False)
+class SingleKind:
+    """A kind of surface that is traced as ONE launch of its own between two fused runs, never
+    inside a fused range: what the Python layers need to know about it, stated once."""
+
+    name: str           # trace_<name>, can_trace_<name>, ol_trace_<name>, has_trace_<name>
+    geoms: tuple        # its GEOM_* codes
+    rows: str           # the SystemTable property that lists its rows
+    switch: str | None  # the pack_surfaces / enable keyword, the _SG key, traces_<switch> and
+    #                     OPTILAND_HIP_<SWITCH>; None: served whenever the pack tolerates
+    wavelength: bool    # the entry takes `double wavelength_um` behind the wavelength index
+    row_noun: str       # "surface 3 is not <row_noun> row of this table"
+    noun: str           # "polarisation-dependent coating on <noun>"
+    unserved: str       # "<unserved> is not on the fused path"
+
+
+KIND_FORBES = SingleKind("forbes", (GEOM_FORBES_Q, GEOM_FORBES_Q2D), "forbes", None, False,
+                         "a Forbes", "a Forbes surface", "Forbes geometry")
+KIND_GRATING = SingleKind("grating", (GEOM_PLANE_GRATING, GEOM_STANDARD_GRATING), "gratings",
+                          "gratings", True, "a grating", "a grating", "a grating")
+KIND_PHASE = SingleKind("phase", (GEOM_PLANE_PHASE,), "phases", "phases", True,
+                        "a phase", "a phase surface", "a phase surface")
+KIND_GRID_SAG = SingleKind("grid_sag", (GEOM_GRID_SAG,), "grid_sag_rows", "grid_sags", False,
+                           "a grid-sag", "a grid-sag surface", "a grid-sag surface")
+SINGLE_KINDS = (KIND_FORBES, KIND_GRATING, KIND_PHASE, KIND_GRID_SAG)
+KIND_OF_GEOM = {g: k for k in SINGLE_KINDS for g in k.geoms}
+
 # numpy image of `ol_surface_desc`; align=True reproduces the C layout.
 SURFACE_DESC_DTYPE = np.dtype(
     [
@@ -197,50 +225,51 @@ class SystemTable:
         return bool(np.any(self.surfaces["coating_kind"] == COAT_RETARDER))
 
     @property
+    def single_rows(self) -> dict:
+        """Row index -> `SingleKind` of every row that is one launch of its own between two fused
+        runs (`HipSystem.trace` splits a range there).  Disjoint from `unsupported`, whose rows
+        are placeholders nobody launches."""
+        memo = self.__dict__.get("_single_rows")
+        if memo is None:
+            memo = self.__dict__["_single_rows"] = {
+                i: KIND_OF_GEOM[g] for i, g in enumerate(self.surfaces["geom_kind"].tolist())
+                if g in KIND_OF_GEOM}
+        return memo
+
+    @property
+    def singles(self) -> tuple:
+        """The indices of `single_rows`, ascending."""
+        memo = self.__dict__.get("_singles")
+        if memo is None:
+            memo = self.__dict__["_singles"] = tuple(self.single_rows)
+        return memo
+
+    def _rows_of(self, kind: SingleKind) -> tuple:
+        return tuple(i for i, k in self.single_rows.items() if k is kind)
+
+    @property
     def forbes(self) -> tuple:
         """Indices of the Forbes rows (GEOM_FORBES_Q / GEOM_FORBES_Q2D): each is one
-        `ol_trace_forbes` launch between two fused runs (`HipSystem.trace` splits a range there).
-        Disjoint from `unsupported`, whose rows are placeholders nobody launches."""
-        memo = self.__dict__.get("_forbes")
-        if memo is None:
-            g = self.surfaces["geom_kind"]
-            memo = self.__dict__["_forbes"] = tuple(
-                int(i) for i in np.nonzero((g == GEOM_FORBES_Q) | (g == GEOM_FORBES_Q2D))[0])
-        return memo
+        `ol_trace_forbes` launch between two fused runs."""
+        return self._rows_of(KIND_FORBES)
 
     @property
     def gratings(self) -> tuple:
         """Indices of the grating rows (GEOM_PLANE_GRATING / GEOM_STANDARD_GRATING): each is one
-        `ol_trace_grating` launch between two fused runs, like the Forbes rows."""
-        memo = self.__dict__.get("_gratings")
-        if memo is None:
-            g = self.surfaces["geom_kind"]
-            memo = self.__dict__["_gratings"] = tuple(
-                int(i) for i in np.nonzero((g == GEOM_PLANE_GRATING)
-                                           | (g == GEOM_STANDARD_GRATING))[0])
-        return memo
+        `ol_trace_grating` launch between two fused runs."""
+        return self._rows_of(KIND_GRATING)
 
     @property
     def phases(self) -> tuple:
         """Indices of the phase-profile rows (GEOM_PLANE_PHASE): each is one `ol_trace_phase`
-        launch between two fused runs, like the grating rows."""
-        memo = self.__dict__.get("_phases")
-        if memo is None:
-            g = self.surfaces["geom_kind"]
-            memo = self.__dict__["_phases"] = tuple(
-                int(i) for i in np.nonzero(g == GEOM_PLANE_PHASE)[0])
-        return memo
+        launch between two fused runs."""
+        return self._rows_of(KIND_PHASE)
 
     @property
     def grid_sag_rows(self) -> tuple:
         """Indices of the grid-sag rows (GEOM_GRID_SAG): each is one `ol_trace_grid_sag` launch
-        between two fused runs, like the Forbes rows."""
-        memo = self.__dict__.get("_grid_sag_rows")
-        if memo is None:
-            g = self.surfaces["geom_kind"]
-            memo = self.__dict__["_grid_sag_rows"] = tuple(
-                int(i) for i in np.nonzero(g == GEOM_GRID_SAG)[0])
-        return memo
+        between two fused runs."""
+        return self._rows_of(KIND_GRID_SAG)
 
     def reference_newton_surfaces(self, first: int = 0, last: int | None = None) -> list:
         """Traced Newton-Raphson surfaces of [first, last] that carry SURF_REFERENCE_NEWTON (the

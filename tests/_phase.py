@@ -337,60 +337,11 @@ def make_engine_class(exe: str, tmp_dir):
     """`OracleEngine` (tests/_fake_engine.py) for the fused runs + the host checker for the phase
     rows, joined by the product's own splitter (`optiland_amd.engine.split_trace`): what
     `HipSystem.trace` does on a range with phase rows, on CPU tensors."""
-    import torch
+    from tests._fake_engine import single_kind_engine_class
 
-    from optiland_amd.engine import TraceResult, split_trace
-    from tests._fake_engine import OracleEngine
+    def step(engine, planes, surface, wavelength_index):
+        path = os.path.join(str(tmp_dir), f"engine_{id(engine)}.case")
+        write_case(path, engine.table, planes, surface=surface, wl_index=wavelength_index)
+        return host_step(exe, path)[0]
 
-    class PhaseOracleEngine(OracleEngine):
-        phase_launches = 0
-
-        def can_trace_phase(self):
-            return True
-
-        def trace_phase(self, rays, surface, wavelength_index=0, record_row=None,
-                        write_rays=None, midrange=False, **_):
-            type(self).phase_launches += 1
-            n = int(rays[0].numel())
-            path = os.path.join(str(tmp_dir), f"engine_{id(self)}.case")
-            write_case(path, self.table, np.stack([t.double().numpy() for t in rays]),
-                       surface=int(surface), wl_index=int(wavelength_index))
-            got, _bits = host_step(exe, path)
-            new = torch.as_tensor(got, dtype=rays[0].dtype)
-            if record_row is not None:
-                record_row[:, :n].copy_(new)
-            if write_rays or (write_rays is None and record_row is None):
-                for k in range(8):
-                    rays[k].copy_(new[k])
-            return 0
-
-        def trace(self, rays, wavelength_index=0, record=True, prt=None, first=0, last=None,
-                  write_rays=None, check_status=True, prt_identity=False,
-                  nonunit_directions=False):
-            last = self.num_surfaces - 1 if last is None else last
-            if not any(first <= f <= last for f in self.table.phases):
-                return super().trace(rays, wavelength_index, record, prt, first, last, write_rays,
-                                     check_status, prt_identity, nonunit_directions)
-            assert prt is None, "the bridge keeps polarised bundles off the phase kernel"
-            rays = list(rays)
-            n = int(rays[0].numel())
-            rec = record if isinstance(record, torch.Tensor) else (
-                self.alloc_record(n, rays[0].dtype, last - first + 1) if record is True else None)
-            if write_rays is None:
-                write_rays = rec is None
-            work = rays if write_rays else [t.clone() for t in rays]
-            base = super()
-
-            def fused(a, b, view, r0, midrange):
-                assert r0 is None or r0 == a
-                base.trace(work, wavelength_index, record=view if view is not None else False,
-                           first=a, last=b, write_rays=True)
-
-            def one(s, row, midrange):
-                self.trace_phase(work, s, wavelength_index, record_row=row, write_rays=True,
-                                 midrange=midrange)
-
-            split_trace(self.table.phases, first, last, rec, first, fused, one)
-            return TraceResult(n, rays, rec, None, 0, first, last)
-
-    return PhaseOracleEngine
+    return single_kind_engine_class(S.KIND_PHASE, step)

@@ -277,6 +277,57 @@ def test_split_trace_walks_runs_and_rows_in_order():
                      ("fused", 2, 3, None, None, False)]
 
 
+def test_trace_dispatches_every_single_kind_in_one_table():
+    """One table with all four one-launch kinds (nothing is launched: only `geom_kind` matters):
+    the rows each kind owns, and which `trace_<name>` serves which row of a split range."""
+    import torch
+
+    from optiland_amd.engine import HipSystem
+
+    kinds = [S.GEOM_PLANE, S.GEOM_FORBES_Q, S.GEOM_STANDARD, S.GEOM_FORBES_Q2D,
+             S.GEOM_PLANE_GRATING, S.GEOM_STANDARD_GRATING, S.GEOM_STANDARD, S.GEOM_PLANE_PHASE,
+             S.GEOM_GRID_SAG, S.GEOM_PLANE]
+    desc = np.zeros(len(kinds), dtype=S.SURFACE_DESC_DTYPE)
+    desc["geom_kind"] = kinds
+    table = S.SystemTable(surfaces=desc, coeffs=np.zeros(0),
+                          optics=np.zeros((len(kinds), 1), dtype=S.SURFACE_OPTICS_DTYPE),
+                          wavelengths=np.array([0.55]))
+    assert table.forbes == (1, 3) and table.gratings == (4, 5)
+    assert table.phases == (7,) and table.grid_sag_rows == (8,)
+    assert table.singles == (1, 3, 4, 5, 7, 8)
+    assert {i: k.name for i, k in table.single_rows.items()} == {
+        1: "forbes", 3: "forbes", 4: "grating", 5: "grating", 7: "phase", 8: "grid_sag"}
+
+    hs = HipSystem.__new__(HipSystem)
+    hs.device = torch.device("cpu")
+    hs._status = torch.zeros(1, dtype=torch.int32)
+    hs.table = table
+    calls = []
+
+    def recorder(name):
+        def launch(rays, surface, wavelength_index=0, midrange=False, **_):
+            calls.append((name, surface, midrange))
+        return launch
+
+    for name in ("forbes", "grating", "phase", "grid_sag"):
+        setattr(hs, "trace_" + name, recorder(name))
+
+    def fused(rays, wavelength_index=0, first=0, last=None, _status_to=None, **_):
+        # (`_trace_split` gives a fused run a status word of its own exactly when it is midrange)
+        calls.append(("fused", first, last, _status_to is not None))
+
+    hs.trace = fused
+    planes = [torch.zeros(3, dtype=torch.float64) for _ in range(8)]
+    HipSystem.trace(hs, planes, first=0, last=9, record=False)
+    assert calls == [("fused", 0, 0, True), ("forbes", 1, True), ("fused", 2, 2, True),
+                     ("forbes", 3, True), ("grating", 4, True), ("grating", 5, True),
+                     ("fused", 6, 6, True), ("phase", 7, True), ("grid_sag", 8, True),
+                     ("fused", 9, 9, False)]
+    with pytest.raises(ValueError):
+        HipSystem.trace(hs, planes, first=0, last=9, record=False,
+                        prt=torch.zeros((9, 3), dtype=torch.float64))
+
+
 # ------------------------------------------------------------------ with the live reference
 @pytest.fixture(scope="module")
 def ref():
