@@ -103,3 +103,82 @@ def test_mpmath_huygens_field_agrees_with_the_direct_sum(gen):
     field, scale = gen.mp_huygens(*few)
     assert np.array_equal(field, g["golden/field"][:2])
     assert np.array_equal(scale, g["golden/scale"][:2])
+
+
+# ---- tests/golden/exact_trace.npz (tools/make_golden_exact_trace.py, tests/_exact_trace.py) ----
+from tests import _exact_trace as X  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def gen_trace():
+    pytest.importorskip("mpmath")
+    spec = importlib.util.spec_from_file_location(
+        "make_golden_exact_trace", os.path.join(ROOT, "tools", "make_golden_exact_trace.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_exact_trace_fixture_holds_what_the_trace_tests_read():
+    g = X.load()
+    assert os.path.getsize(X.GOLD) < 1 << 20
+    for name in X.CASES:
+        for tag in X.TAGS:
+            table = X.case_table(name, tag)
+            rows, inputs = table.num_surfaces, g[f"{name}/{tag}/in"]
+            n = inputs.shape[1]
+            assert inputs.shape == (7, n) and inputs.dtype == X.NP_DTYPE[tag] and n <= 132
+            assert g[f"{name}/{tag}/truth"].shape == (rows - 1, 8, n)
+            keep = g[f"{name}/{tag}/keep"]
+            # at most a tenth of the bundle is dropped, and what is kept is a whole ray
+            assert keep.dtype == bool and n - int(keep.sum()) <= X.MAX_DROPPED * n, (name, tag)
+            truth = X.truth_of(g, name, tag)
+            assert np.isfinite(truth[:, :, keep]).all() and np.all(truth[:, 6, keep] > 0)
+            for key in ("yard", "scale") + (("ref",) if tag == "f64" else ()):
+                a = g[f"{name}/{tag}/{key}"]
+                assert a.shape == (rows, 4) and np.isfinite(a).all() and np.all(a >= 0), key
+            for key in ("kappa", "znorm"):
+                a = g[f"{name}/{tag}/{key}"]
+                assert a.shape == (rows,) and np.isfinite(a).all() and np.all(a >= 0), key
+            newton = np.isin(table.surfaces["geom_kind"], X.NEWTON)
+            assert np.all(g[f"{name}/{tag}/kappa"][newton] > 0)
+            assert np.all(table.surfaces["tol"][newton] == X.NEWTON_TOL[tag])
+    # every Newton kind has a case of its own, and both stored forms of the Zernike surface
+    kinds = {int(k) for name in X.HAND for k in X.case_table(name, "f64").surfaces["geom_kind"]}
+    assert set(X.NEWTON) <= kinds
+
+
+def test_five_rays_of_every_exact_trace_case_are_made_again_bit_for_bit(gen_trace):
+    g = X.load()
+    for name in X.CASES:
+        for tag in X.TAGS:
+            n = g[f"{name}/{tag}/in"].shape[1]
+            only = [0, 7, n // 2, n - 5, n - 1]
+            made = gen_trace.make(name, tag, only=only)
+            assert made[f"{name}/{tag}/in"].tobytes() == g[f"{name}/{tag}/in"].tobytes(), name
+            a, b = made[f"{name}/{tag}/truth"][:, :, only], g[f"{name}/{tag}/truth"][:, :, only]
+            assert a.tobytes() == b.tobytes(), (name, tag)
+
+
+def test_exact_trace_truth_agrees_with_the_oracle():
+    """The truth's own conventions -- root choice, sign of the normal, path length, frames --
+    against the oracle at the tolerances the suite holds the fp64 kernels to: 1e-9 of the
+    group's scale on conic systems, 1e-7 behind a Newton surface (2e-8 on the near-flat sphere,
+    where the oracle's quadratic cancels: tests/test_gpu_edge_cases.py)."""
+    from oracle import oracle
+    from tests._util import PLANES
+    g = X.load()
+    for name in X.CASES:
+        table = X.case_table(name, "f64")
+        keep = g[f"{name}/f64/keep"]
+        rays = {k: g[f"{name}/f64/in"][j] for j, k in enumerate(PLANES[:7])}
+        ref = oracle.trace(table, rays, 0, record=True)["record"]
+        truth = X.truth_of(g, name, "f64")
+        newton = np.isin(table.surfaces["geom_kind"], X.NEWTON).any()
+        tol = 2e-8 if name == "near_flat" else (1e-7 if newton else 1e-9)
+        err = X.group_max(ref - truth, keep).max(axis=0)
+        scale = np.maximum(X.group_max(truth, keep).max(axis=0), [0, 1, 0, 0])
+        print(f"\n[truth vs oracle] {name}: " + " ".join(
+            f"{grp} {e / s:.1e}" for grp, e, s in zip(X.GROUPS, err, scale)) + f" (tol {tol:g})")
+        assert np.all(err <= tol * scale), (name, err / scale)
+        assert np.array_equal(np.isnan(ref[:, :, keep]), np.isnan(truth[:, :, keep]))
