@@ -1328,10 +1328,7 @@ int ol_trace_ex(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* const r
   if (int rc = rule_count("ol_trace", n_rays, "negative ray count")) return rc;
   if (int rc = rule_range("ol_trace", v, first_surface, last_surface)) return rc;
   if (int rc = rule_wavelength("ol_trace", v.n_wl, wavelength_index)) return rc;
-  if (int rc = rule_no_forbes("ol_trace", v, first_surface, last_surface)) return rc;
-  if (int rc = rule_no_grating("ol_trace", v, first_surface, last_surface)) return rc;
-  if (int rc = rule_no_phase("ol_trace", v, first_surface, last_surface)) return rc;
-  if (int rc = rule_no_grid_sag("ol_trace", v, first_surface, last_surface)) return rc;
+  if (int rc = rule_no_single_kinds("ol_trace", v, first_surface, last_surface)) return rc;
   if (n_rays == 0) return OL_OK;
   if (int rc = rule_current_device("ol_trace", v)) return rc;
   if (int rc = rule_planes("ol_trace", "rays", rays, 8)) return rc;
@@ -1367,10 +1364,7 @@ int ol_newton_count(const ol_system* sys, ol_dtype dt, int64_t n_rays, void* con
   if (int rc = rule_range("ol_newton_count", v, first_surface, surface)) return rc;
   if (int rc = rule_wavelength("ol_newton_count", v.n_wl, wavelength_index)) return rc;
   if (!iterations) return failf(OL_EINVAL, "ol_newton_count: iterations is NULL");
-  if (int rc = rule_no_forbes("ol_newton_count", v, first_surface, surface)) return rc;
-  if (int rc = rule_no_grating("ol_newton_count", v, first_surface, surface)) return rc;
-  if (int rc = rule_no_phase("ol_newton_count", v, first_surface, surface)) return rc;
-  if (int rc = rule_no_grid_sag("ol_newton_count", v, first_surface, surface)) return rc;
+  if (int rc = rule_no_single_kinds("ol_newton_count", v, first_surface, surface)) return rc;
   if (!v.ref_newton[surface])
     return failf(OL_EINVAL, "ol_newton_count: surface %d is not a traced Newton-Raphson surface "
                             "with OL_SURF_REFERENCE_NEWTON", surface);

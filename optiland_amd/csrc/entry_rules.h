@@ -92,54 +92,42 @@ inline int rule_retarder_needs_complex(const char* who, const SystemView& v, int
   return OL_OK;
 }
 
-// Forbes rows (OL_GEOM_FORBES_Q / _Q2D) are traced by ol_trace_forbes alone (forbes.hip): the
-// fused kernels carry no functor for them, so every entry point that walks a surface range
-// answers a range that holds one here, before any launch
-inline int rule_no_forbes(const char* who, const SystemView& v, int32_t first, int32_t last) {
-  for (int32_t s = first; s <= last; ++s)
-    if (is_forbes_kind(v.geom[s]))
-      return failf(OL_EUNSUPPORTED, "%s: surface %d is a Forbes surface: trace it with "
-                                    "ol_trace_forbes and cut the range there", who, s);
-  return OL_OK;
-}
+// The one-launch surface kinds, each traced by an entry of its own (forbes.hip, grating.hip,
+// phase.hip, grid_sag.hip: one launch between two fused runs).  The fused kernels carry no functor
+// for them -- they would refract at a grating or a phase surface -- so every entry point that
+// walks a surface range answers a range that holds one, before any launch.  The order of the
+// table is the order in which the kinds are looked for.
+struct SingleKind {
+  const char* entry;            // the one entry point that traces the kind
+  bool (*is_kind)(int32_t);     // on an ol_geom_kind
+  const char* row;              // "surface 3 is not a <row>": what that entry asks its row to be
+  const char* found;            // "surface 3 is <found>": what a range is told it holds
+  bool takes_wavelength_um;     // the entry has a wavelength_um argument
+};
+enum { kSingleForbes, kSingleGrating, kSinglePhase, kSingleGridSag, kSingleKindCount };
+constexpr SingleKind kSingleKinds[kSingleKindCount] = {
+    {"ol_trace_forbes", is_forbes_kind, "Forbes surface", "a Forbes surface", false},
+    {"ol_trace_grating", is_grating_kind, "grating", "a diffraction grating", true},
+    {"ol_trace_phase", is_phase_kind, "phase surface", "a phase surface", true},
+    {"ol_trace_grid_sag", is_grid_sag_kind, "grid-sag surface", "a grid-sag surface", false},
+};
 
-// grating rows (OL_GEOM_PLANE_GRATING / _STANDARD_GRATING) likewise: ol_trace_grating alone
-// (grating.hip) diffracts, the fused kernels would refract
-inline int rule_no_grating(const char* who, const SystemView& v, int32_t first, int32_t last) {
-  for (int32_t s = first; s <= last; ++s)
-    if (is_grating_kind(v.geom[s]))
-      return failf(OL_EUNSUPPORTED, "%s: surface %d is a diffraction grating: trace it with "
-                                    "ol_trace_grating and cut the range there", who, s);
-  return OL_OK;
-}
-
-// phase-profile rows (OL_GEOM_PLANE_PHASE) likewise: ol_trace_phase alone (phase.hip) adds the
-// gradient of the phase, the fused kernels would refract
-inline int rule_no_phase(const char* who, const SystemView& v, int32_t first, int32_t last) {
-  for (int32_t s = first; s <= last; ++s)
-    if (is_phase_kind(v.geom[s]))
-      return failf(OL_EUNSUPPORTED, "%s: surface %d is a phase surface: trace it with "
-                                    "ol_trace_phase and cut the range there", who, s);
-  return OL_OK;
-}
-
-// grid-sag rows (OL_GEOM_GRID_SAG) likewise: ol_trace_grid_sag alone (grid_sag.hip) knows the
-// table of sag values, the fused kernels have no functor for it
-inline int rule_no_grid_sag(const char* who, const SystemView& v, int32_t first, int32_t last) {
-  for (int32_t s = first; s <= last; ++s)
-    if (is_grid_sag_kind(v.geom[s]))
-      return failf(OL_EUNSUPPORTED, "%s: surface %d is a grid-sag surface: trace it with "
-                                    "ol_trace_grid_sag and cut the range there", who, s);
+// kinds outer, surfaces inner: a range that holds two kinds names the row of the kind that comes
+// first in the table, not the row that comes first in the range
+inline int rule_no_single_kinds(const char* who, const SystemView& v, int32_t first,
+                                int32_t last) {
+  for (const SingleKind& k : kSingleKinds)
+    for (int32_t s = first; s <= last; ++s)
+      if (k.is_kind(v.geom[s]))
+        return failf(OL_EUNSUPPORTED, "%s: surface %d is %s: trace it with %s and cut the range "
+                                      "there", who, s, k.found, k.entry);
   return OL_OK;
 }
 
 // the fused entry points (one launch: generate -> trace [-> reduce]) walk the whole system and do
 // not serve ranges whose Newton iteration count is a property of the batch
 inline int rule_no_reference_newton(const char* who, const SystemView& v) {
-  if (int rc = rule_no_forbes(who, v, 0, v.n_surf - 1)) return rc;
-  if (int rc = rule_no_grating(who, v, 0, v.n_surf - 1)) return rc;
-  if (int rc = rule_no_phase(who, v, 0, v.n_surf - 1)) return rc;
-  if (int rc = rule_no_grid_sag(who, v, 0, v.n_surf - 1)) return rc;
+  if (int rc = rule_no_single_kinds(who, v, 0, v.n_surf - 1)) return rc;
   for (int32_t s = 0; s < v.n_surf; ++s)
     if (v.ref_newton[s])
       return failf(OL_EUNSUPPORTED, "%s: the system carries OL_SURF_REFERENCE_NEWTON surfaces "

@@ -39,23 +39,13 @@ inline int aim_check(const ol_system* sys, int64_t n_rays, int32_t wavelength_in
   if (std::isnan(p->stop_radius) || std::isnan(p->jacobian))
     return failf(OL_EINVAL, "ol_aim_rays: stop_radius %g / jacobian %g is NaN", p->stop_radius,
                  p->jacobian);
-  // (this entry words the two range rules its own way)
-  for (int32_t s = first_surface; s <= stop_surface; ++s)
-    if (is_forbes_kind(v.geom[s]))
-      return failf(OL_EUNSUPPORTED, "ol_aim_rays: surface %d is a Forbes surface (traced by "
-                                    "ol_trace_forbes only)", s);
-  for (int32_t s = first_surface; s <= stop_surface; ++s)
-    if (is_grating_kind(v.geom[s]))
-      return failf(OL_EUNSUPPORTED, "ol_aim_rays: surface %d is a diffraction grating (traced by "
-                                    "ol_trace_grating only)", s);
-  for (int32_t s = first_surface; s <= stop_surface; ++s)
-    if (is_phase_kind(v.geom[s]))
-      return failf(OL_EUNSUPPORTED, "ol_aim_rays: surface %d is a phase surface (traced by "
-                                    "ol_trace_phase only)", s);
-  for (int32_t s = first_surface; s <= stop_surface; ++s)
-    if (is_grid_sag_kind(v.geom[s]))
-      return failf(OL_EUNSUPPORTED, "ol_aim_rays: surface %d is a grid-sag surface (traced by "
-                                    "ol_trace_grid_sag only)", s);
+  // (this entry words the two range rules its own way; the kinds in the order of
+  // rule_no_single_kinds)
+  for (const SingleKind& k : kSingleKinds)
+    for (int32_t s = first_surface; s <= stop_surface; ++s)
+      if (k.is_kind(v.geom[s]))
+        return failf(OL_EUNSUPPORTED, "ol_aim_rays: surface %d is %s (traced by %s only)", s,
+                     k.found, k.entry);
   // a batch-global stop rule has no per-ray form
   for (int32_t s = first_surface; s <= stop_surface; ++s)
     if (v.ref_newton[s])

@@ -23,7 +23,7 @@ struct SystemView {
   const int32_t* coating;
   const uint8_t* ref_newton;         // OL_SURF_REFERENCE_NEWTON on a traced Newton surface
   const int32_t* geom;               // ol_geom_kind as given, [n_surf]
-  const DevSurfHot<float>* surf32;   // the fp32 table (the one-surface units: forbes.hip, ...)
+  const DevSurfHot<float>* surf32;   // the fp32 table (single_surface.h: rows_of<float>)
   const DevSurfCold<float>* cold32;
   const DevOptics<float>* optics32;
   const float* coeffs32;

@@ -46,7 +46,8 @@ def _copy(table: SystemTable) -> SystemTable:
 def tables() -> dict:
     """name -> SystemTable: a plain lens, one with Fresnel coatings, one with a retarder, one with
     OL_SURF_REFERENCE_NEWTON on a traced Newton surface, a second lens of another size (optics_of),
-    the aiming fixture's lens, and the Forbes singlet plain and with a Fresnel coating."""
+    the aiming fixture's lens, the Forbes singlet plain and with a Fresnel coating, and a table
+    with a grating row in front of a Forbes row (TWO_KINDS)."""
     from tests import _forbes, _ray_aim
 
     out = {"plain": load_system("double_gauss"), "fresnel": load_system("zernike_fresnel_fringe"),
@@ -64,7 +65,24 @@ def tables() -> dict:
     coated = _copy(out["forbes"])
     coated.surfaces["coating_kind"][_forbes.FORBES] = S.COAT_FRESNEL
     out["forbes_coated"] = coated
+    out["two_kinds"] = two_kinds_table()
     return out
+
+
+def two_kinds_table() -> SystemTable:
+    """The grating fixture's table with the Forbes fixture's Forbes row appended behind it -- its
+    coefficient block behind the grating's, its offset shifted: the kind that is refused LATER (the
+    grating) sits at the LOWER surface index."""
+    from tests import _forbes, _grating
+
+    g, f = _copy(_grating.case("flat_t")["table"]), _forbes.case("q_norm12_default")["table"]
+    assert g.optics.shape[1] == f.optics.shape[1]
+    row = f.surfaces[_forbes.FORBES:_forbes.FORBES + 1].copy()
+    row["coeff_offset"] += g.coeffs.size
+    g.surfaces = np.concatenate([g.surfaces, row])
+    g.optics = np.concatenate([g.optics, f.optics[_forbes.FORBES:_forbes.FORBES + 1]])
+    g.coeffs = np.concatenate([np.asarray(g.coeffs, dtype=np.float64), f.coeffs])
+    return g
 
 
 def _raygen_params(table: SystemTable) -> _capi.RaygenParams:
@@ -190,6 +208,13 @@ def trace_ex(k, a):
                              k.record if a["record"] else None, a["stride"],
                              k.prt if a["prt"] else None, a["first"], a["last"], a["flags"],
                              k.status, _ref(ex), None)
+
+
+def trace(k, a):
+    return k.lib.ol_trace(k.handle(a), a["dt"], a["n"], _planes(k.rays, a["rays"]), a["wl"],
+                          k.record if a["record"] else None, a["stride"],
+                          k.prt if a["prt"] else None, a["first"], a["last"], a["flags"], k.status,
+                          None)
 
 
 def newton_count(k, a):
@@ -439,6 +464,32 @@ DEVICE_ENTRIES = {
         + _holes("out", 6) + _holes("guess", 6),
         accepted=("no rays",)),
 }
+
+# A range that holds rows of two one-launch kinds answers the kind that is refused first (Forbes,
+# then grating, phase, grid sag), not the surface that comes first: [entry, call, arguments].  The
+# table has the grating at row 3 and the Forbes row at row 5; the answers of the parent commit are
+# the fixture's section "two_kinds".
+TWO_KINDS = [
+    ["ol_trace", trace, dict(sys="two_kinds", dt=F64, n=N, rays=OK, wl=0, record=True, stride=N,
+                             prt=False, first=0, last=5, flags=0)],
+    ["ol_trace behind the grating", trace,
+     dict(sys="two_kinds", dt=F64, n=N, rays=OK, wl=0, record=True, stride=N, prt=False, first=4,
+          last=5, flags=0)],
+    ["ol_trace in front of the forbes row", trace,
+     dict(sys="two_kinds", dt=F64, n=N, rays=OK, wl=0, record=True, stride=N, prt=False, first=0,
+          last=4, flags=0)],
+    ["ol_newton_count", newton_count, dict(sys="two_kinds", dt=F64, n=N, rays=OK, wl=0, first=0,
+                                           surface=5, iterations=True)],
+    ["ol_trace_generate", trace_generate,
+     dict(sys="two_kinds", dt=F64, n=N, p=True, wl=0, record=True, stride=N, rays_out=None,
+          prt=False, flags=0, extras=None, **{"in": OK})],
+]
+
+
+def two_kinds(k: Context) -> list:
+    """[[case, return code, text], ...] of TWO_KINDS."""
+    return [[case, *_answer(k, {"call": call}, a)] for case, call, a in TWO_KINDS]
+
 
 # the current-device rule, recorded and replayed only where two devices are visible
 OTHER_DEVICE = "other device current"

@@ -116,7 +116,7 @@ def build_program(name: str, src: str, force: bool = False, verbose: bool = Fals
     # program that is up to date)
     deps = [os.path.join(CSRC, d) for d in DEPS] + [
         src, os.path.join(HERE, "harness.hip"), os.path.join(ROOT, "include", "optiland_hip.h"),
-        os.path.abspath(__file__)]
+        os.path.join(ROOT, "tests", "hostsingle", "host_common.h"), os.path.abspath(__file__)]
     if not force and os.path.exists(exe) and \
             all(os.path.getmtime(d) <= os.path.getmtime(exe) for d in deps):
         return exe

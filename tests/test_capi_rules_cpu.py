@@ -33,6 +33,23 @@ def test_fixture_names_its_parent_and_every_entry():
             assert all((rc == 0) == (text == R.OK) for _case, rc, text in cases), name
 
 
+def test_a_range_of_two_kinds_answers_the_kind_refused_first(context):
+    """A grating row in front of a Forbes row: the range-walking entries name the Forbes row, as
+    the parent did (the kinds are walked one after the other, each over the whole range), and the
+    grating only where the range holds no Forbes row."""
+    fix = R.fixture()
+    assert len(fix["parent"]["two_kinds"]) == 40
+    want = fix["two_kinds"]
+    assert [c[0] for c in want] == [c[0] for c in R.TWO_KINDS]
+    assert R.two_kinds(context) == want
+    texts = {case: text for case, _rc, text in want}
+    assert all(rc == -2 for _case, rc, _text in want)
+    for case in ("ol_trace", "ol_newton_count", "ol_trace_generate"):
+        assert "surface 5 is a Forbes surface" in texts[case], case
+    assert "surface 3 is a diffraction grating" in texts["ol_trace in front of the forbes row"]
+    assert "surface 5 is a Forbes surface" in texts["ol_trace behind the grating"]
+
+
 def test_host_entries_refuse_what_the_parent_refused(context):
     """Code and text of every case, exactly; every peeling sequence ends with an accepted call."""
     section = R.fixture()["host"]

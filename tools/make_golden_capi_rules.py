@@ -12,6 +12,10 @@ before any source edit -- and writes down each return code and ol_last_error tex
                                                     library on a GPU (OPTILAND_HIP_LIBRARY names
                                                     the library of the pinned commit)
 
+    python tools/make_golden_capi_rules.py two_kinds  a range that holds rows of two one-launch
+                                                    kinds (tests/_capi_rules.py: TWO_KINDS),
+                                                    through the host-math library (CPU only)
+
 Each run replaces its own section of the file and keeps the other.  `--commit HASH` names the
 pinned commit (default: HEAD of a clean tree).
 """
@@ -60,7 +64,7 @@ def record(k: R.Context, entries: dict) -> dict:
 
 def main():
     section = sys.argv[1] if len(sys.argv) > 1 else ""
-    if section not in ("host", "device"):
+    if section not in ("host", "device", "two_kinds"):
         sys.exit(__doc__)
     commit = _commit()
     if section == "host":
@@ -68,6 +72,14 @@ def main():
 
         k = R.Context(_hostmath.load(), R.numpy_put)
         got = record(k, R.ENTRIES)
+    elif section == "two_kinds":
+        from tests import _hostmath
+
+        k = R.Context(_hostmath.load(), R.numpy_put)
+        got = R.two_kinds(k)
+        for case, rc, text in got:
+            print(f"{case:40s} {rc:3d} {text}")
+            assert rc != 0 and text, (case, "was accepted")
     else:
         import torch
 
@@ -93,8 +105,8 @@ def main():
     with open(R.GOLD, "w") as f:
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write("\n")
-    print(f"{R.GOLD}: {sum(len(v) for v in got.values())} cases of {len(got)} entries ({section}), "
-          f"commit {commit}")
+    cases = len(got) if section == "two_kinds" else sum(len(v) for v in got.values())
+    print(f"{R.GOLD}: {cases} cases ({section}), commit {commit}")
 
 
 if __name__ == "__main__":
