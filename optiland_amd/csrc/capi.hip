@@ -1,26 +1,27 @@
 // capi.hip -- the C ABI declared in include/optiland_hip.h.
 //
-// Host-side only: validates arguments, re-expresses the public surface table as
+// Host-side only: validates arguments, uploads the staged surface table as
 // DevSurf<T>/DevOptics<T> for T in {float, double} (device_table.h) and launches
 // the kernels on the caller's stream.  No ray memory is ever allocated here.
+// Staging -- the public table re-expressed in double, and everything it refuses -- is
+// system_stage.h (with zernike_stage.h and the kind table geom_kinds.h), host-only headers.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <new>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/optiland_hip.h"
 #include "device_table.h"
 #include "entry_rules.h"
 #include "last_error.h"
+#include "system_stage.h"
 #include "system_view.h"
 #include "trace_launch.h"
 
@@ -49,186 +50,6 @@ using namespace ol;   // failf and the shared argument rules (entry_rules.h)
       return failf(OL_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
   } while (0)
 
-void mat3_mul_abt(const double* A, const double* B, double* out) {  // A * B^T
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double acc = 0;
-      for (int k = 0; k < 3; ++k) acc += A[3 * i + k] * B[3 * j + k];
-      out[3 * i + j] = acc;
-    }
-}
-
-bool is_identity(const double* R) {
-  static const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  return std::memcmp(R, I, sizeof(I)) == 0 ||
-         std::equal(R, R + 9, I);  // -0.0 == 0.0
-}
-
-// device form of a leaf aperture: squared radii, inverse squared semi-axes
-void convert_aperture(int kind, const double* a, double* out) {
-  out[0] = out[1] = out[2] = out[3] = 0.0;
-  switch (kind) {
-    case OL_AP_RADIAL:
-    case OL_AP_OFFSET_RADIAL:
-      out[0] = a[0] * a[0];
-      out[1] = a[1] * a[1];
-      out[2] = a[2];
-      out[3] = a[3];
-      break;
-    case OL_AP_RECTANGULAR:
-      for (int k = 0; k < 4; ++k) out[k] = a[k];
-      break;
-    case OL_AP_ELLIPTICAL:
-      out[0] = 1.0 / (a[0] * a[0]);
-      out[1] = 1.0 / (a[1] * a[1]);
-      out[2] = a[2];
-      out[3] = a[3];
-      break;
-    default:
-      break;
-  }
-}
-
-double factorial(int n) {
-  double f = 1.0;
-  for (int i = 2; i <= n; ++i) f *= i;
-  return f;
-}
-
-// Regroup Zernike terms (c_j, n_j, m_j, N_j) into one LEVEL per azimuthal order |m| with
-// the (cos, sin) radial polynomials in u = rho^2, the factor rho^|m| removed:
-//   R_n^m(rho) = sum_k (-1)^k (n-k)! / (k! ((n+m)/2-k)! ((n-m)/2-k)!) rho^(n-2k)
-// (zernike/base.py:216-239), rho^(n-2k) = rho^m u^((n-m)/2-k).
-// Layout per level (device_table.h): [m, K] as integers (their slots are recorded in
-// `int_slots` and uploaded as bit patterns), then K x {a_c, a_s, b_c, b_s, d_c, d_s}.
-int build_zernike_block(const double* terms, int n_terms, std::vector<double>& out,
-                        std::vector<size_t>& int_slots, int* n_levels) {
-  struct Level { std::vector<double> a[2], b[2]; };
-  std::map<int, Level> levels;
-  for (int j = 0; j < n_terms; ++j) {
-    const double c = terms[4 * j];
-    const int n = (int)terms[4 * j + 1];
-    const int m = (int)terms[4 * j + 2];
-    const double N = terms[4 * j + 3];
-    if (c == 0.0) continue;  // zernike.py:234 (and contributes 0 to the sag)
-    const int ma = std::abs(m);
-    if (n < ma || ((n - ma) & 1) || n > 60) return -1;
-    const int K = (n - ma) / 2 + 1;
-    Level& lv = levels[ma];
-    const int kind = m < 0 ? 1 : 0;
-    for (int q = 0; q < 2; ++q)
-      if ((int)lv.a[q].size() < K) {
-        lv.a[q].resize(K, 0.0);
-        lv.b[q].resize(K, 0.0);
-      }
-    for (int k = 0; k < K; ++k) {
-      double coef = ((k & 1) ? -1.0 : 1.0) * factorial(n - k) /
-                    (factorial(k) * factorial((n + ma) / 2 - k) * factorial((n - ma) / 2 - k));
-      const int p = (n - ma) / 2 - k;
-      lv.a[kind][p] += c * N * coef;
-      lv.b[kind][p] += c * coef;
-    }
-  }
-  *n_levels = (int)levels.size();
-  for (auto& kv : levels) {  // std::map iterates in ascending m
-    const Level& lv = kv.second;
-    const int K = (int)lv.a[0].size();
-    int_slots.push_back(out.size());
-    out.push_back((double)kv.first);
-    int_slots.push_back(out.size());
-    out.push_back((double)K);
-    for (int k = 0; k < K; ++k) {
-      out.push_back(lv.a[0][k]);
-      out.push_back(lv.a[1][k]);
-      out.push_back(lv.b[0][k]);
-      out.push_back(lv.b[1][k]);
-      out.push_back(k + 1 < K ? (k + 1) * lv.b[0][k + 1] : 0.0);
-      out.push_back(k + 1 < K ? (k + 1) * lv.b[1][k + 1] : 0.0);
-    }
-  }
-  return 0;
-}
-
-// Low-order Zernike surfaces as ONE bivariate polynomial in the normalised Cartesian
-// coordinates (device_table.h: kGeomZernikeMono).  Every term is expanded,
-//   rho^m cos(m phi) = Re (x + i y)^m,   rho^m sin(m phi) = Im (x + i y)^m,
-//   R_n^m(rho) rho^-m = sum_k r_k (x^2 + y^2)^((n-m)/2-k)          (zernike/base.py:216-239)
-// into the monomials x^i y^j, i + j <= n: S (with the normalisation constants N_j, the
-// sag, zernike.py:153-180) and Q (without them: what the reference differentiates for the
-// normal, zernike.py:234-240); the block holds S and the two derivative triangles of Q in
-// Horner order.  The expansion is exact up to rounding in double.  Conditioning: on the unit
-// circle sum |s_ij| |x|^i |y|^j of one term is sum_k |r_k| (|x| + |y|)^m -- the radial
-// polynomial's own growth, which the per-|m| level form has too, times at most 2^(m/2)
-// from the binomial expansion of the harmonic (the level form builds the harmonics by a
-// stable recurrence instead).  The degree cap keeps that extra factor at <= 16; higher
-// orders stay on the level form.  Returns false when the surface has to stay there.
-constexpr int kZernMonoMaxDegree = 8;
-
-// OPTILAND_HIP_ZERNIKE_MONO=0 keeps every Zernike surface on the level form (A/B runs,
-// parity tests of the level evaluator on low-order systems)
-bool zernike_mono_enabled() {
-  const char* e = getenv("OPTILAND_HIP_ZERNIKE_MONO");
-  return !(e && e[0] == '0');
-}
-
-double binomial(int n, int k) { return factorial(n) / (factorial(k) * factorial(n - k)); }
-
-bool build_zernike_mono_block(const double* terms, int n_terms, std::vector<double>& out,
-                              int* degree) {
-  int nmax = -1;
-  for (int j = 0; j < n_terms; ++j) {
-    if (terms[4 * j] == 0.0) continue;
-    const int n = (int)terms[4 * j + 1], ma = std::abs((int)terms[4 * j + 2]);
-    if (n < ma || ((n - ma) & 1) || n > kZernMonoMaxDegree) return false;
-    nmax = std::max(nmax, n);
-  }
-  if (nmax < 0) return false;  // no term at all: the level form handles "nothing" already
-  const int W = nmax + 1;
-  std::vector<double> S(W * W, 0.0), Q(W * W, 0.0);  // [i * W + j] = coefficient of x^i y^j
-  for (int t = 0; t < n_terms; ++t) {
-    const double c = terms[4 * t];
-    if (c == 0.0) continue;
-    const int n = (int)terms[4 * t + 1], m = (int)terms[4 * t + 2], ma = std::abs(m);
-    const double N = terms[4 * t + 3];
-    for (int k = 0; k <= (n - ma) / 2; ++k) {
-      const double rk = ((k & 1) ? -1.0 : 1.0) * factorial(n - k) /
-                        (factorial(k) * factorial((n + ma) / 2 - k) * factorial((n - ma) / 2 - k));
-      const int pw = (n - ma) / 2 - k;  // power of u = x^2 + y^2
-      for (int q = 0; q <= pw; ++q) {   // u^pw = sum_q C(pw, q) x^(2 (pw - q)) y^(2 q)
-        const double uq = binomial(pw, q);
-        // harmonic part: cos -> even powers of y, sin -> odd powers of y
-        for (int h = (m < 0 ? 1 : 0); h <= ma; h += 2) {
-          const double sign = ((h / 2) & 1) ? -1.0 : 1.0;  // i^h: +1, (+i), -1, (-i), ...
-          const double hc = binomial(ma, h) * sign;
-          const int i = 2 * (pw - q) + (ma - h), jj = 2 * q + h;
-          S[i * W + jj] += c * N * rk * uq * hc;
-          Q[i * W + jj] += c * rk * uq * hc;
-        }
-      }
-    }
-  }
-  // Horner order: outer in x from the highest power, inner in y from the highest power
-  for (int i = nmax; i >= 0; --i)
-    for (int j = nmax - i; j >= 0; --j) out.push_back(S[i * W + j]);
-  for (int i = nmax - 1; i >= 0; --i)
-    for (int j = nmax - 1 - i; j >= 0; --j) {
-      out.push_back((i + 1) * Q[(i + 1) * W + j]);  // dQ/dx
-      out.push_back((j + 1) * Q[i * W + j + 1]);    // dQ/dy
-    }
-  *degree = nmax;
-  return true;
-}
-
-// host-side staging record: every field of both device blocks, in double
-struct HostSurf {
-  int32_t geom, interaction, aperture_kind, coating_kind, coeff_off, n_coeff, max_iter;
-  uint32_t flags;
-  int32_t poly_cols, coeff_len, ap_off, ap_len;
-  double cv, kp1, tol, inv_norm;
-  double origin[3], rot[9], rel_off[3], rel_rot[9], ap[4], coat[2], axis[3], ret_cos, ret_sin;
-  double radius, conic;
-};
-
 template <typename T>
 struct DeviceTable {
   // ONE allocation: [hot rows | cold rows | optics rows | coefficients], each block on a
@@ -245,16 +66,6 @@ struct DeviceTable {
 
 inline size_t round256(size_t v) { return (v + 255u) & ~size_t(255u); }
 
-// everything ol_system_create derives from its arguments, in double, before any device call
-struct Staged {
-  std::vector<struct HostSurf> surf;
-  std::vector<ol::DevOptics<double>> optics;
-  std::vector<double> coeffs;
-  std::vector<size_t> int_slots;  // coeffs entries uploaded as integer bit patterns
-  std::vector<int32_t> interaction, coating, geom;
-  std::vector<uint8_t> polygon, ref_newton, no_pair;
-};
-
 }  // namespace
 
 struct ol_system {
@@ -263,14 +74,7 @@ struct ol_system {
   int device = 0;
   DeviceTable<float> f32;
   DeviceTable<double> f64;
-  std::vector<int32_t> interaction;  // host copy for validation
-  std::vector<int32_t> coating;
-  std::vector<int32_t> geom;
-  std::vector<uint8_t> polygon;  // surface uses a polygon aperture (top level or in a tree)
-  std::vector<uint8_t> ref_newton;  // OL_SURF_REFERENCE_NEWTON on a traced Newton-Raphson surface
-  // the surface keeps a polarised Zernike launch off the two-rays-per-lane form
-  // (trace_kernel.hip: OL_POLZ_PAIR): a Zernike surface in the level form, a polarizer / retarder
-  std::vector<uint8_t> no_pair;
+  HostFacts facts;   // host copies for validation (system_stage.h)
   // false between the two in-place uploads of ol_system_update and for good if the second
   // one fails: the fp32 and fp64 tables (and the host copies) then describe different
   // prescriptions -- every entry point refuses such a system instead of tracing through it
@@ -367,10 +171,10 @@ int newton_family(const ol_system* sys, int32_t first, int32_t last) {
   // OL_SURF_REFERENCE_NEWTON (opt-in, ABI 11) on any Newton surface of the range: the kernel
   // family that iterates the batch in lockstep (surface_math.h: newton_reference)
   for (int32_t s = first; s <= last; ++s)
-    if (sys->ref_newton[s]) return ol::kNrReference;
+    if (sys->facts.ref_newton[s]) return ol::kNrReference;
   for (int32_t s = first; s <= last; ++s) {
-    polygon = polygon || sys->polygon[s];
-    const int g = sys->geom[s];
+    polygon = polygon || sys->facts.polygon[s];
+    const int g = sys->facts.geom[s];
     if (g == OL_GEOM_PLANE || g == OL_GEOM_STANDARD) continue;
     any = true;
     all_zernike = all_zernike && g == OL_GEOM_ZERNIKE;
@@ -426,7 +230,7 @@ int do_trace(const ol_system* sys, const DeviceTable<T>& tab, int64_t n, void* c
   // Zero-copy object row: when the caller's ray planes ARE row 0 of the record
   // block and the first surface only records (ObjectSurface.trace,
   // surfaces/object_surface.py:56-69), the kernel skips that row's stores.
-  if (record && a.record_from == first && sys->interaction[first] == OL_INTERACT_RECORD_ONLY) {
+  if (record && a.record_from == first && sys->facts.interaction[first] == OL_INTERACT_RECORD_ONLY) {
     bool alias = true;
     for (int k = 0; k < 8; ++k)
       alias = alias && (static_cast<T*>(rays[k]) == static_cast<T*>(record) + k * record_stride);
@@ -552,7 +356,7 @@ int do_trace_generate(const ol_system* sys, const DeviceTable<T>& tab, int64_t n
   if (family == ol::kNrZernike) {
     // the polarised Zernike pair (fp32): polynomial-form Zernike surfaces, real diagonal Jones
     // matrices, an even number of rays (the PRT planes are written with 8-byte lane accesses)
-    for (int32_t s = 0; s < sys->n_surf; ++s) pair_ok = pair_ok && !sys->no_pair[s];
+    for (int32_t s = 0; s < sys->n_surf; ++s) pair_ok = pair_ok && !sys->facts.no_pair[s];
     pair_ok = pair_ok && prt && n % 2 == 0 && reinterpret_cast<uintptr_t>(prt) % 8 == 0 &&
               reinterpret_cast<uintptr_t>(a.i_updated) % 8 == 0;
   }
@@ -747,8 +551,8 @@ namespace ol {
 SystemView system_view(const ol_system* sys) {
   return SystemView{sys->n_surf,        sys->n_wl,      sys->device,
                     sys->consistent,    sys->f64.surf,  sys->f64.cold,
-                    sys->f64.optics,    sys->f64.coeffs, sys->interaction.data(),
-                    sys->coating.data(), sys->ref_newton.data(), sys->geom.data(),
+                    sys->f64.optics,    sys->f64.coeffs, sys->facts.interaction.data(),
+                    sys->facts.coating.data(), sys->facts.ref_newton.data(), sys->facts.geom.data(),
                     sys->f32.surf,      sys->f32.cold,  sys->f32.optics,
                     sys->f32.coeffs};
 }
@@ -789,457 +593,6 @@ int ol_set_tuning(int32_t knob, int32_t value) {
   }
 }
 
-namespace {
-// The self-describing block of an OL_GEOM_PLANE_PHASE row (ol_geom_kind in optiland_hip.h), checked
-// value by value and appended to `out` in the layout phase_device.h reads.  src: the row's
-// s.n_coeff values (inside the buffer: the caller checked the range).
-int stage_phase_block(int32_t i, const ol_surface_desc& s, const double* src, int32_t n_wl,
-                      std::vector<double>& out, std::vector<size_t>& int_slots) {
-  const int64_t n = s.n_coeff;
-  // a count stored as a double: whole, not negative, no larger than the block itself
-  auto whole = [&](double c, int64_t& v) {
-    if (!(c >= 0.0) || c > (double)n || c != std::floor(c)) return false;
-    v = (int64_t)c;
-    return true;
-  };
-  if (s.interaction == OL_INTERACT_RECORD_ONLY)
-    return failf(OL_EUNSUPPORTED, "surface %d: a phase surface that only records", i);
-  int64_t kind = 0;
-  if (n < 2 || !whole(src[0], kind) || kind > 3)
-    return failf(OL_EINVAL, "surface %d: phase profile kind %g is not 0 (constant), 1 (linear), "
-                            "2 (radial) or 3 (grid)", i, n >= 1 ? src[0] : -1.0);
-  if (!std::isfinite(src[1]))
-    return failf(OL_EINVAL, "surface %d: phase profile efficiency %g must be finite", i, src[1]);
-  const size_t base = out.size();
-  int_slots.push_back(base);
-  if (kind == ol::kPhaseConstant || kind == ol::kPhaseLinear) {
-    const int64_t need = kind == ol::kPhaseConstant ? 3 : 4;
-    if (n != need)
-      return failf(OL_EINVAL, "surface %d: a %s phase block holds %lld values, not %lld", i,
-                   kind == ol::kPhaseConstant ? "constant" : "linear", (long long)need,
-                   (long long)n);
-    out.insert(out.end(), src, src + n);
-    return OL_OK;
-  }
-  if (kind == ol::kPhaseRadial) {
-    int64_t count = 0;
-    if (n < 3 || !whole(src[2], count) || 3 + count != n)
-      return failf(OL_EINVAL, "surface %d: radial phase block of %lld values does not match the "
-                              "term count %g it declares", i, (long long)n, n >= 3 ? src[2] : -1.0);
-    int_slots.push_back(base + 2);
-    out.insert(out.end(), src, src + n);
-    return OL_OK;
-  }
-  int64_t W = 0, H = 0, n_scale = 0;
-  if (n < 9 || !whole(src[2], W) || !whole(src[3], H) || W < 2 || H < 2)
-    return failf(OL_EINVAL, "surface %d: a phase grid needs whole node counts W, H >= 2 (got %g, "
-                            "%g)", i, n >= 9 ? src[2] : -1.0, n >= 9 ? src[3] : -1.0);
-  for (int k = 4; k < 8; ++k)
-    if (!std::isfinite(src[k]))
-      return failf(OL_EINVAL, "surface %d: phase grid bound %g is not finite", i, src[k]);
-  if (src[5] == src[4] || src[7] == src[6])
-    return failf(OL_EINVAL, "surface %d: phase grid bounds coincide (x %g .. %g, y %g .. %g)", i,
-                 src[4], src[5], src[6], src[7]);
-  if (!whole(src[8], n_scale) || (n_scale != 0 && n_scale != n_wl))
-    return failf(OL_EINVAL, "surface %d: phase grid scale count %g is neither 0 nor the "
-                            "wavelength count %d", i, src[8], n_wl);
-  if (9 + n_scale + W * H != n)
-    return failf(OL_EINVAL, "surface %d: phase grid block of %lld values does not match the "
-                            "counts it declares (9 + %lld scales + %lld x %lld nodes)", i,
-                 (long long)n, (long long)n_scale, (long long)W, (long long)H);
-  const double xs = src[5] - src[4], ys = src[7] - src[6];
-  const double head[ol::kPhaseGridHead] = {
-      src[0], src[1], (double)W, (double)H, src[4], xs, src[6], ys, (double)(W - 1),
-      (double)(H - 1), (double)(W - 1) / xs, (double)(H - 1) / ys, (double)n_scale};
-  out.insert(out.end(), head, head + ol::kPhaseGridHead);
-  int_slots.push_back(base + 2);
-  int_slots.push_back(base + 3);
-  int_slots.push_back(base + 12);
-  out.insert(out.end(), src + 9, src + n);
-  return OL_OK;
-}
-
-// The self-describing block of an OL_GEOM_GRID_SAG row (ol_geom_kind in optiland_hip.h), checked
-// value by value and appended to `out` in the layout grid_sag_device.h reads.  src: the row's
-// s.n_coeff values (inside the buffer: the caller checked the range).
-int stage_grid_sag_block(int32_t i, const ol_surface_desc& s, const double* src,
-                         std::vector<double>& out, std::vector<size_t>& int_slots) {
-  const int64_t n = s.n_coeff;
-  auto whole = [&](double c, int64_t& v) {
-    if (!(c >= 0.0) || c > (double)n || c != std::floor(c)) return false;
-    v = (int64_t)c;
-    return true;
-  };
-  if (s.interaction == OL_INTERACT_RECORD_ONLY)
-    return failf(OL_EUNSUPPORTED, "surface %d: a grid-sag surface that only records", i);
-  int64_t W = 0, H = 0;
-  if (n < 2 || !whole(src[0], W) || !whole(src[1], H) || W < 2 || H < 2)
-    return failf(OL_EINVAL, "surface %d: a sag grid needs whole node counts W, H >= 2 (got %g, "
-                            "%g)", i, n >= 2 ? src[0] : -1.0, n >= 2 ? src[1] : -1.0);
-  // (the last cell, W - 2, is a float in the fp32 table: exact up to 2^24)
-  if (W > (1 << 24) || H > (1 << 24))
-    return failf(OL_EINVAL, "surface %d: a sag grid takes at most 16777216 nodes on an axis (got "
-                            "%lld, %lld)", i, (long long)W, (long long)H);
-  if (2 + W + H + W * H != n)
-    return failf(OL_EINVAL, "surface %d: sag grid block of %lld values does not match the counts "
-                            "it declares (2 + %lld + %lld coordinates + %lld x %lld nodes)", i,
-                 (long long)n, (long long)W, (long long)H, (long long)W, (long long)H);
-  for (int64_t k = 2; k < n; ++k)
-    if (!std::isfinite(src[k]))
-      return failf(OL_EINVAL, "surface %d: sag grid value %lld (%g) is not finite", i,
-                   (long long)k, src[k]);
-  const double* xs = src + 2;
-  const double* ys = xs + W;
-  auto increasing = [&](const double* v, int64_t cnt, const char* axis) {
-    for (int64_t k = 1; k < cnt; ++k)
-      if (!(v[k] > v[k - 1]) || !((float)v[k] > (float)v[k - 1]))
-        return failf(OL_EINVAL, "surface %d: sag grid %s coordinates are not strictly increasing "
-                                "(as doubles and as floats) at index %lld: %.17g, %.17g", i, axis,
-                     (long long)k, v[k - 1], v[k]);
-    return (int)OL_OK;
-  };
-  if (int rc = increasing(xs, W, "x")) return rc;
-  if (int rc = increasing(ys, H, "y")) return rc;
-  const size_t base = out.size();
-  const double head[ol::kGridSagHead] = {
-      (double)W, (double)H, (double)(W - 2), (double)(H - 2), xs[0], xs[W - 1], ys[0], ys[H - 1],
-      (double)(W - 1) / (xs[W - 1] - xs[0]), (double)(H - 1) / (ys[H - 1] - ys[0])};
-  out.insert(out.end(), head, head + ol::kGridSagHead);
-  int_slots.push_back(base);
-  int_slots.push_back(base + 1);
-  out.insert(out.end(), src + 2, src + n);
-  return OL_OK;
-}
-
-// argument validation + every host-side conversion of ol_system_create / ol_system_update
-int stage_system(const char* who, const ol_surface_desc* surf, int32_t n_surf,
-                 const double* coeffs, int32_t n_coeffs, const ol_surface_optics* optics,
-                 int32_t n_wavelengths, Staged& st) {
-  if (!surf || n_surf <= 0) return failf(OL_EINVAL, "%s: no surfaces", who);
-  if (!optics || n_wavelengths <= 0) return failf(OL_EINVAL, "%s: no optics table", who);
-  if (n_coeffs < 0 || (n_coeffs > 0 && !coeffs))
-    return failf(OL_EINVAL, "%s: bad coefficient buffer", who);
-
-  st.surf.assign(n_surf, HostSurf());
-  std::vector<HostSurf>& dev = st.surf;
-  std::vector<double>& dcoef = st.coeffs;
-  std::vector<size_t>& int_slots = st.int_slots;
-  int32_t prev_traced = -1;
-  for (int32_t i = 0; i < n_surf; ++i) {
-    const ol_surface_desc& s = surf[i];
-    HostSurf& d = dev[i];
-    std::memset(&d, 0, sizeof(d));
-    if (s.geom_kind < OL_GEOM_PLANE || s.geom_kind > OL_GEOM_GRID_SAG ||
-        s.geom_kind == 13 || s.geom_kind == 15)   // (13, 15: never assigned, refused as always)
-      return failf(OL_EUNSUPPORTED, "surface %d: geometry kind %d", i, s.geom_kind);
-    if (s.interaction < OL_INTERACT_RECORD_ONLY || s.interaction > OL_INTERACT_REFLECT)
-      return failf(OL_EUNSUPPORTED, "surface %d: interaction %d", i, s.interaction);
-    if (s.aperture_kind < OL_AP_NONE || s.aperture_kind > OL_AP_POLYGON)
-      return failf(OL_EUNSUPPORTED, "surface %d: aperture kind %d", i, s.aperture_kind);
-    if (s.coating_kind < OL_COAT_NONE || s.coating_kind > OL_COAT_RETARDER)
-      return failf(OL_EUNSUPPORTED, "surface %d: coating kind %d", i, s.coating_kind);
-    if (s.n_coeff < 0 || s.coeff_offset < 0)
-      return failf(OL_EINVAL, "surface %d: negative coefficient range", i);
-    const int per = s.geom_kind == OL_GEOM_ZERNIKE ? 4 : 1;
-    const int extra = s.geom_kind == OL_GEOM_CHEBYSHEV ? 2 : 0;
-    if ((int64_t)s.coeff_offset + (int64_t)s.n_coeff * per + extra > n_coeffs)
-      return failf(OL_EINVAL, "surface %d: coefficient block exceeds the buffer", i);
-
-    d.geom = s.geom_kind;
-    if (s.geom_kind == OL_GEOM_FORBES_Q) d.geom = ol::kGeomForbesQ;   // (9 is kGeomZernikeMono)
-    if (s.geom_kind == OL_GEOM_FORBES_Q2D) d.geom = ol::kGeomForbesQ2d;
-    if (s.geom_kind == OL_GEOM_PLANE_GRATING) d.geom = ol::kGeomPlaneGrating;
-    if (s.geom_kind == OL_GEOM_STANDARD_GRATING) d.geom = ol::kGeomStandardGrating;
-    if (s.geom_kind == OL_GEOM_PLANE_PHASE) d.geom = ol::kGeomPlanePhase;
-    if (s.geom_kind == OL_GEOM_GRID_SAG) d.geom = ol::kGeomGridSag;
-    d.interaction = s.interaction;
-    d.aperture_kind = s.aperture_kind;
-    d.coating_kind = s.coating_kind;
-    d.max_iter = s.max_iter;
-    d.poly_cols = s.poly_cols;
-    d.flags = (s.flags & OL_SURF_ROTATED) ? ol::kSurfRotated : 0u;
-    const bool inf_r = std::isinf(s.radius) || s.geom_kind == OL_GEOM_PLANE ||
-                       s.geom_kind == OL_GEOM_PLANE_GRATING || s.geom_kind == OL_GEOM_PLANE_PHASE ||
-                       s.geom_kind == OL_GEOM_GRID_SAG;   // (a grid has no base conic)
-    if (inf_r) d.flags |= ol::kSurfRadiusInf;
-    if ((s.flags & OL_SURF_REFERENCE_ROOT) && !inf_r &&
-        (s.geom_kind == OL_GEOM_STANDARD || s.geom_kind == OL_GEOM_STANDARD_GRATING))
-      d.flags |= ol::kSurfReferenceRoot;
-    d.cv = inf_r ? 0.0 : 1.0 / s.radius;
-    d.kp1 = 1.0 + s.conic;
-    d.radius = s.radius;
-    d.conic = s.conic;
-    d.tol = s.tol;
-    d.inv_norm = s.norm_radius != 0.0 ? 1.0 / s.norm_radius : 0.0;
-    for (int k = 0; k < 3; ++k) d.origin[k] = s.origin[k];
-    for (int k = 0; k < 9; ++k) d.rot[k] = s.rot[k];
-    if (!(d.flags & ol::kSurfRotated)) {
-      static const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-      std::memcpy(d.rot, I, sizeof(I));
-    }
-    // relative transform from the local frame of the previous TRACED surface (the
-    // kernel keeps its state in that frame; record-only surfaces do not move it)
-    static const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    std::memcpy(d.rel_rot, I, sizeof(I));
-    if (prev_traced >= 0) {
-      const HostSurf& p = dev[prev_traced];
-      mat3_mul_abt(d.rot, p.rot, d.rel_rot);
-      double dv[3] = {p.origin[0] - d.origin[0], p.origin[1] - d.origin[1],
-                      p.origin[2] - d.origin[2]};
-      for (int r = 0; r < 3; ++r) {
-        double v = d.rot[3 * r] * dv[0] + d.rot[3 * r + 1] * dv[1] + d.rot[3 * r + 2] * dv[2];
-        d.rel_off[r] = std::isfinite(v) ? v : 0.0;
-      }
-      if (!is_identity(d.rel_rot)) d.flags |= ol::kSurfRelRotated;
-    }
-    if (s.interaction != OL_INTERACT_RECORD_ONLY) prev_traced = i;
-    // apertures: pre-square / pre-invert in double; polygon vertex blocks move into the
-    // device coefficient buffer and their token / descriptor offsets are rewritten
-    auto stage_polygon = [&](const double* a, double* q) -> int {
-      const int64_t voff = (int64_t)a[0], nv = (int64_t)a[1];
-      if (voff < 0 || nv < 1 || voff + 2 * nv > n_coeffs)
-        return failf(OL_EINVAL, "surface %d: polygon vertex block outside the buffer", i);
-      q[0] = (double)dcoef.size();
-      q[1] = (double)nv;
-      q[2] = q[3] = 0.0;
-      dcoef.insert(dcoef.end(), coeffs + voff, coeffs + voff + 2 * nv);
-      return OL_OK;
-    };
-    if (s.aperture_kind == OL_AP_COMPOSITE) {
-      const int64_t off = (int64_t)s.aperture[0], cnt = (int64_t)s.aperture[1];
-      if (off < 0 || cnt <= 0 || off + cnt * OL_AP_TOKEN_DOUBLES > n_coeffs)
-        return failf(OL_EINVAL, "surface %d: aperture token list outside the buffer", i);
-      // pass 1: converted tokens (polygon vertices are appended to dcoef as they come)
-      std::vector<double> toks;
-      int depth = 0;
-      for (int64_t t = 0; t < cnt; ++t) {
-        const double* tok = coeffs + off + t * OL_AP_TOKEN_DOUBLES;
-        const int op = (int)tok[0];
-        double q[4];
-        if (op >= OL_AP_RADIAL && op <= OL_AP_ELLIPTICAL) {
-          convert_aperture(op, tok + 1, q);
-          if (++depth > OL_AP_MAX_DEPTH)
-            return failf(OL_EUNSUPPORTED, "surface %d: aperture tree too deep", i);
-        } else if (op == OL_AP_POLYGON) {
-          if (int rc = stage_polygon(tok + 1, q)) return rc;
-          if (++depth > OL_AP_MAX_DEPTH)
-            return failf(OL_EUNSUPPORTED, "surface %d: aperture tree too deep", i);
-        } else if (op >= OL_AP_OP_UNION && op <= OL_AP_OP_DIFFERENCE) {
-          q[0] = q[1] = q[2] = q[3] = 0.0;
-          if (--depth < 1) return failf(OL_EINVAL, "surface %d: malformed aperture tokens", i);
-        } else {
-          return failf(OL_EUNSUPPORTED, "surface %d: aperture token op %d", i, op);
-        }
-        toks.push_back((double)op);
-        toks.insert(toks.end(), q, q + 4);
-      }
-      if (depth != 1) return failf(OL_EINVAL, "surface %d: malformed aperture tokens", i);
-      // pass 2: the token list itself, contiguous
-      d.ap_off = (int32_t)dcoef.size();
-      d.ap_len = (int32_t)cnt;
-      dcoef.insert(dcoef.end(), toks.begin(), toks.end());
-    } else if (s.aperture_kind == OL_AP_POLYGON) {
-      if (int rc = stage_polygon(s.aperture, d.ap)) return rc;
-    } else {
-      convert_aperture(s.aperture_kind, s.aperture, d.ap);
-    }
-    d.coat[0] = s.coat[0];
-    d.coat[1] = s.coat[1];
-    if (s.coating_kind == OL_COAT_POLARIZER || s.coating_kind == OL_COAT_RETARDER) {
-      const int need = s.coating_kind == OL_COAT_RETARDER ? 4 : 3;
-      const int64_t off = (int64_t)s.coat[0];
-      if (off < 0 || off + need > n_coeffs)
-        return failf(OL_EINVAL, "surface %d: coating axis block outside the buffer", i);
-      for (int k = 0; k < 3; ++k) d.axis[k] = coeffs[off + k];
-      if (s.coating_kind == OL_COAT_RETARDER) {
-        d.ret_cos = std::cos(coeffs[off + 3] / 2);
-        d.ret_sin = std::sin(coeffs[off + 3] / 2);
-      }
-    }
-
-    // coefficient block
-    d.coeff_off = (int32_t)dcoef.size();
-    const double* src = coeffs ? coeffs + s.coeff_offset : nullptr;
-    if (s.geom_kind == OL_GEOM_ZERNIKE) {
-      int ng = 0;
-      if (zernike_mono_enabled() && build_zernike_mono_block(src, s.n_coeff, dcoef, &ng)) {
-        d.geom = ol::kGeomZernikeMono;  // low order, well conditioned: one polynomial
-        d.n_coeff = ng;
-      } else {
-        if (build_zernike_block(src, s.n_coeff, dcoef, int_slots, &ng) != 0)
-          return failf(OL_EINVAL, "surface %d: invalid Zernike (n, m) index", i);
-        d.n_coeff = ng;
-      }
-    } else if (s.geom_kind == OL_GEOM_EVEN_ASPHERE || s.geom_kind == OL_GEOM_ODD_ASPHERE ||
-               s.geom_kind == OL_GEOM_POLYNOMIAL) {
-      if (s.geom_kind == OL_GEOM_POLYNOMIAL &&
-          (s.poly_cols <= 0 || s.n_coeff % s.poly_cols != 0))
-        return failf(OL_EINVAL, "surface %d: polynomial grid %d x ? cols %d", i, s.n_coeff,
-                     s.poly_cols);
-      d.n_coeff = s.n_coeff;
-      dcoef.insert(dcoef.end(), src, src + s.n_coeff);
-    } else if (s.geom_kind == OL_GEOM_CHEBYSHEV) {
-      if (s.poly_cols <= 0 || s.n_coeff % s.poly_cols != 0)
-        return failf(OL_EINVAL, "surface %d: chebyshev grid %d, cols %d", i, s.n_coeff,
-                     s.poly_cols);
-      d.n_coeff = s.n_coeff;
-      dcoef.push_back(1.0 / src[0]);
-      dcoef.push_back(1.0 / src[1]);
-      dcoef.insert(dcoef.end(), src + 2, src + 2 + s.n_coeff);
-    } else if (s.geom_kind == OL_GEOM_BICONIC) {
-      // biconic.py:57-66: cx/cy = 0 for infinite or zero radii
-      if (s.n_coeff != 2) return failf(OL_EINVAL, "surface %d: biconic needs {Ry, ky}", i);
-      const double Rx = s.radius, Ry = src[0];
-      d.cv = (std::isinf(Rx) || Rx == 0.0) ? 0.0 : 1.0 / Rx;
-      d.n_coeff = 2;
-      dcoef.push_back((std::isinf(Ry) || Ry == 0.0) ? 0.0 : 1.0 / Ry);
-      dcoef.push_back(1.0 + src[1]);
-    } else if (s.geom_kind == OL_GEOM_TOROIDAL) {
-      if (s.n_coeff < 2) return failf(OL_EINVAL, "surface %d: toroidal needs {R_rot, k_yz}", i);
-      const double Rr = src[0], Ryz = s.radius;
-      d.n_coeff = s.n_coeff - 2;  // number of y^(2i) terms
-      dcoef.push_back(Rr);
-      dcoef.push_back(std::isinf(Rr) ? 0.0 : 1.0 / Rr);
-      dcoef.push_back(1.0 + src[1]);
-      dcoef.push_back((std::isfinite(Ryz) && Ryz != 0.0) ? 1.0 / Ryz : 0.0);
-      dcoef.insert(dcoef.end(), src + 2, src + s.n_coeff);
-    } else if (ol::is_forbes_kind(s.geom_kind)) {
-      // device block: n0, norm_radius, then the rest of the public block (forbes_device.h)
-      if (!(s.norm_radius > 0.0) || !std::isfinite(s.norm_radius))
-        return failf(OL_EINVAL, "surface %d: Forbes norm_radius %g must be finite and positive", i,
-                     s.norm_radius);
-      if (s.interaction == OL_INTERACT_RECORD_ONLY)
-        return failf(OL_EUNSUPPORTED, "surface %d: a Forbes surface that only records", i);
-      for (int k = 0; k < s.n_coeff; ++k)
-        if (!std::isfinite(src[k]))
-          return failf(OL_EINVAL, "surface %d: Forbes coefficient block entry %d is not finite", i, k);
-      d.n_coeff = s.n_coeff;
-      if (s.geom_kind == OL_GEOM_FORBES_Q) {
-        int_slots.push_back(dcoef.size());
-        dcoef.push_back((double)s.n_coeff);
-        dcoef.push_back(s.norm_radius);
-        dcoef.insert(dcoef.end(), src, src + s.n_coeff);
-      } else {
-        // the block describes itself: walk it once, every count against what is left
-        auto count_at = [&](int64_t at, int64_t& v) {
-          if (at >= s.n_coeff) return false;
-          const double c = src[at];
-          if (!(c >= 0.0) || c > (double)s.n_coeff || c != std::floor(c)) return false;
-          v = (int64_t)c;
-          return true;
-        };
-        const size_t base = dcoef.size();
-        std::vector<size_t> ints;
-        int64_t n0 = 0, M = 0, at = 2;
-        bool ok = count_at(0, n0) && count_at(1, M) && at + n0 <= s.n_coeff;
-        if (ok) {
-          ints.push_back(0);           // n0        (device offsets: + 1 behind norm_radius)
-          ints.push_back(2);           // M
-          at += n0;
-          for (int64_t mm = 0; ok && mm < M; ++mm) {
-            int64_t na = 0, nb = 0;
-            ok = count_at(at, na) && count_at(at + 1, nb) && at + 2 + 4 * (na + nb) <= s.n_coeff;
-            if (ok) {
-              ints.push_back((size_t)at + 1);
-              ints.push_back((size_t)at + 2);
-              at += 2 + 4 * (na + nb);
-            }
-          }
-        }
-        if (!ok || at != s.n_coeff)
-          return failf(OL_EINVAL, "surface %d: Forbes Q2D block of %d values does not match the "
-                                  "counts it declares", i, s.n_coeff);
-        dcoef.push_back(src[0]);
-        dcoef.push_back(s.norm_radius);
-        dcoef.insert(dcoef.end(), src + 1, src + s.n_coeff);
-        for (size_t k : ints) int_slots.push_back(base + k);
-      }
-    } else if (ol::is_grating_kind(s.geom_kind)) {
-      // public block {order, period, groove angle} -> device block (grating_device.h)
-      if (s.n_coeff != 3)
-        return failf(OL_EINVAL, "surface %d: a grating needs {order, period, groove angle}", i);
-      if (s.interaction == OL_INTERACT_RECORD_ONLY)
-        return failf(OL_EUNSUPPORTED, "surface %d: a grating that only records", i);
-      if (!std::isfinite(src[1]) || src[1] == 0.0)
-        return failf(OL_EINVAL, "surface %d: grating period %g must be finite and not zero", i,
-                     src[1]);
-      if (!std::isfinite(src[0]) || !std::isfinite(src[2]))
-        return failf(OL_EINVAL, "surface %d: grating order %g / groove angle %g must be finite", i,
-                     src[0], src[2]);
-      if (s.geom_kind == OL_GEOM_STANDARD_GRATING && (inf_r || !(s.radius != 0.0)))
-        return failf(OL_EINVAL, "surface %d: a standard grating needs a finite radius that is not "
-                                "zero (a flat one is OL_GEOM_PLANE_GRATING)", i);
-      d.n_coeff = 3;
-      dcoef.push_back(src[0]);
-      dcoef.push_back(src[1]);
-      dcoef.push_back(std::sin(src[2]));
-      dcoef.push_back(std::cos(src[2]));
-      dcoef.push_back(std::tan(src[2]));
-    } else if (ol::is_phase_kind(s.geom_kind)) {
-      // public block (ol_geom_kind, include/optiland_hip.h) -> device block (phase_device.h)
-      if (int rc = stage_phase_block(i, s, src, n_wavelengths, dcoef, int_slots)) return rc;
-      d.n_coeff = s.n_coeff;
-    } else if (ol::is_grid_sag_kind(s.geom_kind)) {
-      // public block (ol_geom_kind, include/optiland_hip.h) -> device block (grid_sag_device.h)
-      if (int rc = stage_grid_sag_block(i, s, src, dcoef, int_slots)) return rc;
-      d.n_coeff = s.n_coeff;
-    } else {
-      d.n_coeff = 0;
-    }
-    d.coeff_len = (int32_t)dcoef.size() - d.coeff_off;
-  }
-
-  std::vector<ol::DevOptics<double>>& dopt = st.optics;
-  dopt.assign((size_t)n_surf * n_wavelengths, ol::DevOptics<double>());
-  for (size_t i = 0; i < dopt.size(); ++i) {
-    const ol_surface_optics& o = optics[i];
-    std::memset(&dopt[i], 0, sizeof(dopt[i]));
-    dopt[i].n1 = o.n1;
-    dopt[i].n2 = o.n2;
-    dopt[i].u = o.n1 / o.n2;
-    dopt[i].nn = o.n2 / o.n1;
-    dopt[i].absorb = o.absorb > 0.0 ? o.absorb : 0.0;
-  }
-
-  for (int32_t i = 0; i < n_surf; ++i) {
-    st.interaction.push_back(surf[i].interaction);
-    st.coating.push_back(surf[i].coating_kind);
-    st.geom.push_back(surf[i].geom_kind);
-    {
-      bool poly = surf[i].aperture_kind == OL_AP_POLYGON;
-      if (surf[i].aperture_kind == OL_AP_COMPOSITE) {
-        const int64_t off = (int64_t)surf[i].aperture[0], cnt = (int64_t)surf[i].aperture[1];
-        for (int64_t t = 0; t < cnt; ++t)
-          poly = poly || (int)coeffs[off + t * OL_AP_TOKEN_DOUBLES] == OL_AP_POLYGON;
-      }
-      st.polygon.push_back(poly ? 1 : 0);
-    }
-    st.no_pair.push_back((surf[i].geom_kind == OL_GEOM_ZERNIKE && dev[i].geom != ol::kGeomZernikeMono) ||
-                                 surf[i].coating_kind == OL_COAT_POLARIZER ||
-                                 surf[i].coating_kind == OL_COAT_RETARDER
-                             ? 1 : 0);
-    st.ref_newton.push_back((surf[i].flags & OL_SURF_REFERENCE_NEWTON) &&
-                                    surf[i].geom_kind != OL_GEOM_PLANE &&
-                                    surf[i].geom_kind != OL_GEOM_STANDARD &&
-                                    !ol::is_grating_kind(surf[i].geom_kind) &&
-                                    !ol::is_phase_kind(surf[i].geom_kind) &&
-                                    !ol::is_grid_sag_kind(surf[i].geom_kind) &&
-                                    surf[i].interaction != OL_INTERACT_RECORD_ONLY
-                                ? 1 : 0);
-  }
-  return OL_OK;
-}
-
-void adopt_host_copies(ol_system* sys, Staged& st) {
-  sys->interaction.swap(st.interaction);
-  sys->coating.swap(st.coating);
-  sys->geom.swap(st.geom);
-  sys->polygon.swap(st.polygon);
-  sys->ref_newton.swap(st.ref_newton);
-  sys->no_pair.swap(st.no_pair);
-}
-}  // namespace
-
 int ol_system_create(const ol_surface_desc* surf, int32_t n_surf, const double* coeffs,
                      int32_t n_coeffs, const ol_surface_optics* optics, int32_t n_wavelengths,
                      ol_system** out) {
@@ -1253,7 +606,7 @@ int ol_system_create(const ol_surface_desc* surf, int32_t n_surf, const double* 
   if (!sys) return failf(OL_ENOMEM, "ol_system_create: out of host memory");
   sys->n_surf = n_surf;
   sys->n_wl = n_wavelengths;
-  adopt_host_copies(sys, st);
+  sys->facts = std::move(st.facts);
   if (!current_device(&sys->device)) {
     delete sys;
     return failf(OL_EHIP, "ol_system_create: no HIP device (hipGetDevice failed)");
@@ -1296,7 +649,7 @@ int ol_system_update(ol_system* sys, const ol_surface_desc* surf, int32_t n_surf
   sys->consistent = false;
   rc = upload<float>(st.surf, st.optics, st.coeffs, st.int_slots, sys->f32, true, s);
   if (rc != OL_OK) return rc;
-  adopt_host_copies(sys, st);
+  sys->facts = std::move(st.facts);
   sys->consistent = true;
   return OL_OK;
 }

@@ -15,11 +15,14 @@
 
 // Qualifier of the per-ray arithmetic (surface_math.h, raygen_device.h).  Product build:
 // device code only.  OL_HOST_MATH is defined by tests/hostmath/harness.hip alone, which
-// executes the same functions on the host as a check that needs no GPU.
+// executes the same functions on the host as a check that needs no GPU.  A plain C++ compiler
+// (host-only headers such as system_stage.h, which need the constants below) sees `inline`.
 #ifdef OL_HOST_MATH
 #define OL_DEV __host__ __device__ inline
-#else
+#elif defined(__HIP__)
 #define OL_DEV __device__ __forceinline__
+#else
+#define OL_DEV inline
 #endif
 
 // Table memory as the kernels address it.  In device code every pointer into the surface

@@ -96,7 +96,7 @@ inline int rule_retarder_needs_complex(const char* who, const SystemView& v, int
 // phase.hip, grid_sag.hip: one launch between two fused runs).  The fused kernels carry no functor
 // for them -- they would refract at a grating or a phase surface -- so every entry point that
 // walks a surface range answers a range that holds one, before any launch.  The order of the
-// table is the order in which the kinds are looked for.
+// table (the enumeration kSingle* of geom_kinds.h) is the order in which the kinds are looked for.
 struct SingleKind {
   const char* entry;            // the one entry point that traces the kind
   bool (*is_kind)(int32_t);     // on an ol_geom_kind
@@ -104,7 +104,6 @@ struct SingleKind {
   const char* found;            // "surface 3 is <found>": what a range is told it holds
   bool takes_wavelength_um;     // the entry has a wavelength_um argument
 };
-enum { kSingleForbes, kSingleGrating, kSinglePhase, kSingleGridSag, kSingleKindCount };
 constexpr SingleKind kSingleKinds[kSingleKindCount] = {
     {"ol_trace_forbes", is_forbes_kind, "Forbes surface", "a Forbes surface", false},
     {"ol_trace_grating", is_grating_kind, "grating", "a diffraction grating", true},

@@ -10,11 +10,9 @@
 #include <cstddef>
 
 #include "../../include/optiland_hip.h"
+#include "failf.h"
 
 namespace ol {
-
-// store the formatted message as the text ol_last_error() returns on this thread; returns `code`
-int failf(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // Scratch memory of one entry point, allocated and freed in stream order:
 //   Workspace ws{"ol_x", stream};  if (int rc = ws.alloc(bytes)) return rc;

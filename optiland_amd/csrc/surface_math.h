@@ -597,7 +597,7 @@ OL_DEV void polynomial_eval(const DevSurf<T>& s, cptr<T> c,
 
 // zernike.py:153-252 + zernike/base.py:42-137.  Terms regrouped on the host per
 // azimuthal order m into radial polynomials in u = rho^2 with the factor rho^m taken out
-// (capi.hip:build_zernike_block, layout in device_table.h).  Evaluated in CARTESIAN form:
+// (zernike_stage.h:build_zernike_block, layout in device_table.h).  Evaluated in CARTESIAN form:
 // with the harmonic polynomials
 //     A_m + i B_m = (x_n + i y_n)^m   (= rho^m (cos m phi + i sin m phi)),
 // advanced by one complex multiply per order, the cos and sin terms of one order are
@@ -715,7 +715,7 @@ OL_DEV void zernike_eval(const DevSurf<T>& s, cptr<T> c, T x,
 }
 
 // Low-order Zernike surface as one bivariate polynomial (kGeomZernikeMono, block layout in
-// device_table.h, expansion in capi.hip:build_zernike_mono_block): the sag polynomial S and
+// device_table.h, expansion in zernike_stage.h:build_zernike_mono_block): the sag polynomial S and
 // the gradient (dQ/dx_n, dQ/dy_n) of the normal's polynomial by nested Horner -- outer in
 // x_n, inner in y_n -- straight from the coefficient stream.  One FMA per coefficient for S
 // and one PACKED FMA per coefficient pair for the gradient (v_pk_fma_f32: both partial

@@ -8,6 +8,7 @@
 
 #include "../../include/optiland_hip.h"
 #include "device_table.h"
+#include "geom_kinds.h"
 
 namespace ol {
 
@@ -29,12 +30,11 @@ struct SystemView {
   const float* coeffs32;
 };
 
-inline bool is_forbes_kind(int32_t g) { return g == OL_GEOM_FORBES_Q || g == OL_GEOM_FORBES_Q2D; }
-inline bool is_grating_kind(int32_t g) {
-  return g == OL_GEOM_PLANE_GRATING || g == OL_GEOM_STANDARD_GRATING;
-}
-inline bool is_phase_kind(int32_t g) { return g == OL_GEOM_PLANE_PHASE; }
-inline bool is_grid_sag_kind(int32_t g) { return g == OL_GEOM_GRID_SAG; }
+// on an ol_geom_kind: the one-launch column of geom_kinds.h
+inline bool is_forbes_kind(int32_t g) { return single_kind(g) == kSingleForbes; }
+inline bool is_grating_kind(int32_t g) { return single_kind(g) == kSingleGrating; }
+inline bool is_phase_kind(int32_t g) { return single_kind(g) == kSinglePhase; }
+inline bool is_grid_sag_kind(int32_t g) { return single_kind(g) == kSingleGridSag; }
 
 // `sys` must not be NULL
 SystemView system_view(const ol_system* sys);

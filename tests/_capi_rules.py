@@ -6,6 +6,8 @@ Per entry point: the NULL system, PEELING sequences -- a call that breaks every 
 broken at once with a valid system; the refusal is recorded, exactly the reported fault is
 repaired, and so on until the call is accepted: every text and the order of precedence in about
 as many calls as the entry has rules -- and single-fault calls for what a sequence cannot reach.
+What staging refuses (ol_system_create / ol_system_update, which return at the first fault) is the
+section "create": single-fault calls only (CREATE, UPDATE below).
 
 The fixture tests/golden/capi_rules.json holds, per entry, the list of [case, return code,
 ol_last_error text] ("ok" for an accepted call) as the PARENT commit of the change answered it.
@@ -53,11 +55,7 @@ def tables() -> dict:
     out = {"plain": load_system("double_gauss"), "fresnel": load_system("zernike_fresnel_fringe"),
            "other": load_system("cooke_generic"), "aim": _ray_aim.table("wa100"),
            "forbes": _forbes.case("q_norm12_default")["table"]}
-    ret = _copy(out["plain"])
-    ret.coeffs = np.array([1.0, 0.0, 0.0, np.pi / 2])       # the axis and the retardance
-    ret.surfaces["coating_kind"][2] = S.COAT_RETARDER
-    ret.surfaces["coat"][2] = (0.0, 0.0)
-    out["retarder"] = ret
+    out["retarder"] = retarder_table()
     flagged = _copy(load_system("rc_asphere"))
     k = int(np.nonzero(flagged.surfaces["geom_kind"] == S.GEOM_EVEN_ASPHERE)[0][0])
     flagged.surfaces["flags"][k] |= S.SURF_REFERENCE_NEWTON
@@ -67,6 +65,14 @@ def tables() -> dict:
     out["forbes_coated"] = coated
     out["two_kinds"] = two_kinds_table()
     return out
+
+
+def retarder_table() -> SystemTable:
+    ret = _copy(load_system("double_gauss"))
+    ret.coeffs = np.array([1.0, 0.0, 0.0, np.pi / 2])       # the axis and the retardance
+    ret.surfaces["coating_kind"][2] = S.COAT_RETARDER
+    ret.surfaces["coat"][2] = (0.0, 0.0)
+    return ret
 
 
 def two_kinds_table() -> SystemTable:
@@ -582,3 +588,227 @@ def replay(k: Context, section: dict, entries: dict, report=print) -> int:
     report(f"{count} cases replayed, {len(bad)} differ")
     assert not bad, "\n".join(bad)
     return count
+
+
+# ------------------------------------------------------------------ ol_system_create / _update
+# What STAGING refuses (the host-side conversion of a table, before any device call): single-fault
+# calls -- staging returns at the first fault, so nothing peels -- each next to the accepted
+# neighbour where one exists.  A case: (name, accepted, table, row, fields of that row to set,
+# edits of the call).  Edits: "coeffs" {index: value}, "buffer" (a new coefficient buffer), and the
+# arguments themselves: "surf" / "buffer_ptr" / "optics" None for a NULL pointer, "n_surf",
+# "n_coeffs", "n_wl".  Fields: "aperture[1]" sets one element.  The block rules of the four
+# one-launch kinds are pinned by their own tests (tests/test_*_cpu.py), not here.
+def _golden(name: str) -> SystemTable:
+    return SystemTable.load(os.path.join(HERE, "golden", f"{name}.json"))
+
+
+def create_tables() -> dict:
+    """plain: no coefficients, 3 wavelengths.  boolean: token lists at [0, 35) and [35, 60) of 60.
+    zernike: 12 terms at [0, 48) of 48.  f3: biconic (row 1), toroidal (2, 5), Chebyshev (row 3:
+    9 values, 3 columns, at [6, 17) of 21).  retarder: the axis block [0, 4) of 4, row 2."""
+    return {"plain": load_system("double_gauss"), "boolean": _golden("boolean_apertures"),
+            "zernike": load_system("zernike_fresnel_fringe"), "f3": _golden("f3_family"),
+            "asphere": load_system("rc_asphere"), "retarder": retarder_table()}
+
+
+def _tree(leaves: int, polygon_at: int | None = None) -> list:
+    """`leaves` radial leaves, then the unions that join them: a tree of depth `leaves`.  One leaf
+    may be a polygon of two vertices (its vertex block: the first four values of the buffer)."""
+    toks = [[S.AP_RADIAL, 0.0, 5.0, 0.0, 0.0] for _ in range(leaves)]
+    if polygon_at is not None:
+        toks[polygon_at] = [S.AP_POLYGON, 0.0, 2.0, 0.0, 0.0]
+    toks += [[S.AP_OP_UNION, 0.0, 0.0, 0.0, 0.0]] * (leaves - 1)
+    return [v for t in toks for v in t]
+
+
+def _composite(tokens: list, count: int | None = None):
+    """Row 3 of the plain lens with `tokens` as its aperture."""
+    count = len(tokens) // 5 if count is None else count
+    return ("plain", 3, {"aperture_kind": S.AP_COMPOSITE, "aperture[0]": 0.0,
+                         "aperture[1]": float(count)}, {"buffer": tokens})
+
+
+_SQUARE = [-5.0, -5.0, 5.0, -5.0, 5.0, 5.0, -5.0, 5.0]
+_LEAF, _UNION = _tree(1), [S.AP_OP_UNION, 0.0, 0.0, 0.0, 0.0]
+
+
+def _polygon(voff, nv):
+    return ("plain", 3, {"aperture_kind": S.AP_POLYGON, "aperture[0]": voff, "aperture[1]": nv},
+            {"buffer": _SQUARE})
+
+
+def _polygon_token(voff, nv):   # the first leaf of the boolean table's first list
+    return ("boolean", None, {}, {"coeffs": {0: S.AP_POLYGON, 1: voff, 2: nv}})
+
+
+def _zernike_term(n, m):        # the first term of the Zernike row: (c, n, m, N)
+    return ("zernike", None, {}, {"coeffs": {0: 1.0, 1: n, 2: m}})
+
+
+CREATE = [
+    ("plain", True, "plain", None, {}, {}),
+    ("surfaces NULL", False, "plain", None, {}, {"surf": None}),
+    ("no surfaces", False, "plain", None, {}, {"n_surf": 0}),
+    ("optics NULL", False, "plain", None, {}, {"optics": None}),
+    ("no wavelengths", False, "plain", None, {}, {"n_wl": 0}),
+    ("negative coefficient count", False, "plain", None, {}, {"n_coeffs": -1}),
+    ("coefficients NULL with a count", False, "zernike", None, {}, {"buffer_ptr": None}),
+    # the kinds: below and above their ranges, the two numbers no kind has
+    ("geometry -1", False, "plain", 3, {"geom_kind": -1}, {}),
+    ("geometry 0", True, "plain", 3, {"geom_kind": S.GEOM_PLANE}, {}),
+    ("geometry 13", False, "plain", 3, {"geom_kind": 13}, {}),
+    ("geometry 15", False, "plain", 3, {"geom_kind": 15}, {}),
+    ("geometry 17", False, "plain", 3, {"geom_kind": 17}, {}),
+    ("interaction -1", False, "plain", 3, {"interaction": -1}, {}),
+    ("interaction 2", True, "plain", 3, {"interaction": S.INTERACT_REFLECT}, {}),
+    ("interaction 3", False, "plain", 3, {"interaction": 3}, {}),
+    ("aperture kind -1", False, "plain", 3, {"aperture_kind": -1}, {}),
+    ("aperture kind 7", False, "plain", 3, {"aperture_kind": 7}, {}),
+    ("coating kind -1", False, "plain", 3, {"coating_kind": -1}, {}),
+    ("coating kind 2", True, "plain", 3, {"coating_kind": S.COAT_FRESNEL}, {}),
+    ("coating kind 5", False, "plain", 3, {"coating_kind": 5}, {}),
+    ("negative n_coeff", False, "plain", 3, {"n_coeff": -1}, {}),
+    ("negative coeff_offset", False, "plain", 3, {"coeff_offset": -1}, {}),
+    # a coefficient block against the end of the buffer: four values per Zernike term, two in front
+    # of a Chebyshev grid, one per value otherwise
+    ("zernike block fits exactly", True, "zernike", None, {}, {}),
+    ("zernike block one value short", False, "zernike", None, {}, {"n_coeffs": 47}),
+    ("zernike block one term too many", False, "zernike", 1, {"n_coeff": 13}, {}),
+    ("chebyshev block fits exactly", True, "f3", 3, {"coeff_offset": 10}, {}),
+    ("chebyshev block one value too many", False, "f3", 3, {"coeff_offset": 11}, {}),
+    ("toroidal block fits exactly", True, "f3", None, {}, {}),
+    ("toroidal block one value too many", False, "f3", 5, {"coeff_offset": 20}, {}),
+    ("asphere", True, "asphere", None, {}, {}),
+    # polygon vertex blocks: a top-level aperture, a leaf of a token list
+    ("polygon fits exactly", True, *_polygon(0.0, 4.0)),
+    ("polygon one vertex too many", False, *_polygon(0.0, 5.0)),
+    ("polygon shifted by one value", False, *_polygon(1.0, 4.0)),
+    ("polygon offset -1", False, *_polygon(-1.0, 4.0)),
+    ("polygon without a vertex", False, *_polygon(0.0, 0.0)),
+    ("polygon of one vertex", True, *_polygon(0.0, 1.0)),
+    ("polygon leaf fits exactly", True, *_polygon_token(40.0, 10.0)),
+    ("polygon leaf one vertex too many", False, *_polygon_token(40.0, 11.0)),
+    ("polygon leaf without a vertex", False, *_polygon_token(40.0, 0.0)),
+    # aperture token lists
+    ("token lists fit exactly", True, "boolean", None, {}, {}),
+    ("token list one token too many", False, "boolean", 2, {"aperture[1]": 6.0}, {}),
+    ("token list of no tokens", False, "boolean", 2, {"aperture[1]": 0.0}, {}),
+    ("token list offset -1", False, "boolean", 2, {"aperture[0]": -1.0}, {}),
+    ("tree of depth 16", True, *_composite(_tree(16))),
+    ("tree of depth 17", False, *_composite(_tree(17))),
+    ("tree of depth 16, the last leaf a polygon", True, *_composite(_tree(16, polygon_at=15))),
+    ("tree of depth 17, the last leaf a polygon", False, *_composite(_tree(17, polygon_at=16))),
+    ("one leaf", True, *_composite(_LEAF)),
+    ("two leaves and an operator", True, *_composite(_tree(2))),
+    ("an operator first", False, *_composite(_UNION)),
+    ("an operator behind one leaf", False, *_composite(_LEAF + _UNION)),
+    ("two leaves and no operator", False, *_composite(_LEAF + _LEAF)),
+    ("token op 0", False, *_composite([0.0] * 5)),
+    ("token op 9", False, *_composite([9.0] + [0.0] * 4)),
+    ("token op 13", False, *_composite(_tree(2)[:10] + [13.0] + [0.0] * 4)),
+    # coating axis blocks: three values for a polarizer, four for a retarder
+    ("retarder block fits exactly", True, "retarder", None, {}, {}),
+    ("retarder block one value too many", False, "retarder", 2, {"coat[0]": 1.0}, {}),
+    ("retarder block offset -1", False, "retarder", 2, {"coat[0]": -1.0}, {}),
+    ("polarizer block fits exactly", True, "retarder", 2,
+     {"coating_kind": S.COAT_POLARIZER, "coat[0]": 1.0}, {}),
+    ("polarizer block one value too many", False, "retarder", 2,
+     {"coating_kind": S.COAT_POLARIZER, "coat[0]": 2.0}, {}),
+    # Zernike indices
+    ("zernike n 60", True, *_zernike_term(60.0, 0.0)),
+    ("zernike n 62", False, *_zernike_term(62.0, 0.0)),
+    ("zernike n below |m|", False, *_zernike_term(1.0, -3.0)),
+    ("zernike n - |m| odd", False, *_zernike_term(3.0, 0.0)),
+    ("zernike bad index on a term that is zero", True, "zernike", None, {},
+     {"coeffs": {0: 0.0, 1: 3.0, 2: 0.0}}),
+    # coefficient grids
+    ("chebyshev of one row", True, "f3", 3, {"poly_cols": 9}, {}),
+    ("chebyshev without columns", False, "f3", 3, {"poly_cols": 0}, {}),
+    ("chebyshev ragged", False, "f3", 3, {"poly_cols": 2}, {}),
+    ("polynomial", True, "f3", 3, {"geom_kind": S.GEOM_POLYNOMIAL}, {}),
+    ("polynomial without columns", False, "f3", 3,
+     {"geom_kind": S.GEOM_POLYNOMIAL, "poly_cols": 0}, {}),
+    ("polynomial ragged", False, "f3", 3, {"geom_kind": S.GEOM_POLYNOMIAL, "poly_cols": 2}, {}),
+    # blocks of a fixed shape
+    ("biconic of one value", False, "f3", 1, {"n_coeff": 1}, {}),
+    ("biconic of three values", False, "f3", 1, {"n_coeff": 3}, {}),
+    ("toroidal of one value", False, "f3", 5, {"n_coeff": 1}, {}),
+    ("toroidal without a block", False, "f3", 5, {"n_coeff": 0}, {}),
+]
+
+# ol_system_update on a system made from the f3 table (7 rows, one wavelength; its device block has
+# room for 64 values more): (name, accepted, system given, table, row, fields, edits).  The last
+# toroidal row (2 values at 19) is moved to the end of a longer buffer to grow it.
+_LONG = [0.0] * 21 + [50.0, 0.0] + [0.0] * 65
+
+
+def _grown(terms):
+    return ("f3", 5, {"coeff_offset": 21, "n_coeff": 2 + terms}, {"buffer": _LONG})
+
+
+UPDATE = [
+    ("system NULL", False, False, "f3", None, {}, {}),
+    ("unchanged", True, True, "f3", None, {}, {}),
+    ("one surface fewer", False, True, "f3", None, {}, {"n_surf": 6}),
+    ("one wavelength more", False, True, "f3", None, {}, {"n_wl": 2}),
+    ("surfaces NULL", False, True, "f3", None, {}, {"surf": None}),
+    ("biconic of three values", False, True, "f3", 1, {"n_coeff": 3}, {}),
+    ("block grown by 65 values", False, True, *_grown(65)),
+    ("block grown by 64 values", True, True, *_grown(64)),
+]
+
+
+def _edited(base: SystemTable, row, fields: dict, edits: dict) -> SystemTable:
+    t = _copy(base)
+    t.coeffs = np.array(edits.get("buffer", t.coeffs), dtype=np.float64)
+    for i, v in edits.get("coeffs", {}).items():
+        t.coeffs[i] = v
+    for key, v in fields.items():
+        name, _, index = key.partition("[")
+        if index:
+            t.surfaces[name][row][int(index[:-1])] = v
+        else:
+            t.surfaces[name][row] = v
+    return t
+
+
+def _table_args(t: SystemTable, edits: dict):
+    """(what keeps the arrays alive, the six table arguments of ol_system_create / _update)."""
+    surf, optics = np.ascontiguousarray(t.surfaces), np.ascontiguousarray(t.optics)
+    coeffs = np.ascontiguousarray(t.coeffs, dtype=np.float64)
+    a = {"surf": OK, "n_surf": surf.shape[0], "buffer_ptr": OK if coeffs.size else None,
+         "n_coeffs": coeffs.size, "optics": OK, "n_wl": optics.shape[1], **edits}
+    return (surf, optics, coeffs), (
+        surf.ctypes.data if a["surf"] else None, a["n_surf"],
+        coeffs.ctypes.data if a["buffer_ptr"] else None, a["n_coeffs"],
+        optics.ctypes.data if a["optics"] else None, a["n_wl"])
+
+
+def create(lib) -> list:
+    """[[case, return code, text], ...] of CREATE and UPDATE ("update: ..."); every system an
+    accepted call made is destroyed."""
+    base, out = create_tables(), []
+
+    def answer(rc):
+        return rc, (OK if rc == 0 else lib.ol_last_error().decode("utf-8", "replace"))
+
+    for case, _accepted, name, row, fields, edits in CREATE:
+        keep, args = _table_args(_edited(base[name], row, fields, edits), edits)
+        h = C.c_void_p()
+        out.append([case, *answer(lib.ol_system_create(*args, C.byref(h)))])
+        assert bool(h) == (out[-1][1] == 0), case
+        lib.ol_system_destroy(h)
+    keep, args = _table_args(base["f3"], {})
+    system = C.c_void_p()
+    assert lib.ol_system_create(*args, C.byref(system)) == 0, lib.ol_last_error()
+    for case, _accepted, given, name, row, fields, edits in UPDATE:
+        keep, args = _table_args(_edited(base[name], row, fields, edits), edits)
+        out.append([f"update: {case}",
+                    *answer(lib.ol_system_update(system if given else None, *args, None))])
+    lib.ol_system_destroy(system)
+    return out
+
+
+def create_accepted() -> list:
+    """The case names of create() with whether each is meant to be accepted."""
+    return [(c[0], c[1]) for c in CREATE] + [(f"update: {c[0]}", c[1]) for c in UPDATE]

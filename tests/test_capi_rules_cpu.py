@@ -50,6 +50,19 @@ def test_a_range_of_two_kinds_answers_the_kind_refused_first(context):
     assert "surface 5 is a Forbes surface" in texts["ol_trace behind the grating"]
 
 
+def test_staging_refuses_what_the_parent_refused(context):
+    """ol_system_create / ol_system_update, single-fault calls next to their accepted neighbours
+    (tests/_capi_rules.py: CREATE, UPDATE): code and text of every case as the commit in front of
+    the one that moved staging into csrc/system_stage.h answered it."""
+    fix = R.fixture()
+    assert len(fix["parent"]["create"]) == 40
+    want = fix["create"]
+    assert [(case, rc == 0) for case, rc, _text in want] == R.create_accepted()
+    assert all((rc == 0) == (text == R.OK) for _case, rc, text in want)
+    got = R.create(context.lib)
+    assert [g for g, w in zip(got, want) if g != w] == [] and len(got) == len(want)
+
+
 def test_host_entries_refuse_what_the_parent_refused(context):
     """Code and text of every case, exactly; every peeling sequence ends with an accepted call."""
     section = R.fixture()["host"]

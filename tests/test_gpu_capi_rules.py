@@ -38,6 +38,15 @@ def test_every_entry_refuses_what_the_parent_refused(context):
     assert count == total - len(other) and count > 0
 
 
+def test_staging_refuses_what_the_parent_refused(context):
+    """ol_system_create / ol_system_update through the product library: the tiny tables of
+    tests/_capi_rules.py (CREATE, UPDATE), nothing but create / update / destroy calls."""
+    want = R.fixture()["create"]
+    got = R.create(context.lib)
+    torch.cuda.synchronize()
+    assert [g for g, w in zip(got, want) if g != w] == [] and len(got) == len(want) > 0
+
+
 def test_current_device_rule_with_two_devices(context):
     other = R.fixture()["device"].get("ol_trace_ex")
     if torch.cuda.device_count() < 2 or not other:

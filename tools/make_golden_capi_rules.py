@@ -16,6 +16,11 @@ before any source edit -- and writes down each return code and ol_last_error tex
                                                     kinds (tests/_capi_rules.py: TWO_KINDS),
                                                     through the host-math library (CPU only)
 
+    python tools/make_golden_capi_rules.py create   what staging refuses: single-fault calls of
+                                                    ol_system_create and ol_system_update
+                                                    (tests/_capi_rules.py: CREATE, UPDATE), through
+                                                    the host-math library (CPU only)
+
 Each run replaces its own section of the file and keeps the other.  `--commit HASH` names the
 pinned commit (default: HEAD of a clean tree).
 """
@@ -64,7 +69,7 @@ def record(k: R.Context, entries: dict) -> dict:
 
 def main():
     section = sys.argv[1] if len(sys.argv) > 1 else ""
-    if section not in ("host", "device", "two_kinds"):
+    if section not in ("host", "device", "two_kinds", "create"):
         sys.exit(__doc__)
     commit = _commit()
     if section == "host":
@@ -80,6 +85,16 @@ def main():
         for case, rc, text in got:
             print(f"{case:40s} {rc:3d} {text}")
             assert rc != 0 and text, (case, "was accepted")
+    elif section == "create":
+        from tests import _hostmath
+
+        k = R.Context(_hostmath.load(), R.numpy_put)
+        got = R.create(k.lib)
+        assert [c[0] for c in got] == [c for c, _ in R.create_accepted()]
+        assert len({c[0] for c in got}) == len(got), "case names repeat"
+        for (case, rc, text), (_, accepted) in zip(got, R.create_accepted()):
+            print(f"{case:48s} {rc:3d} {text}")
+            assert text and (rc == 0) == accepted, (case, "accepted" if rc == 0 else "refused")
     else:
         import torch
 
@@ -105,7 +120,7 @@ def main():
     with open(R.GOLD, "w") as f:
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write("\n")
-    cases = len(got) if section == "two_kinds" else sum(len(v) for v in got.values())
+    cases = len(got) if section in ("two_kinds", "create") else sum(len(v) for v in got.values())
     print(f"{R.GOLD}: {cases} cases ({section}), commit {commit}")
 
 
