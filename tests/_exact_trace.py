@@ -291,12 +291,15 @@ def trace_ray(mp, table, ray, wl=0, first=0, last=None, want_kappa=False):
     precision in force.  Returns (rows, info): `rows[k]` the 8 mpf after row first + k (None from
     the row on where the ray is lost), `info` = dict(lost, clipped, min_cos, min_snell, kappa:
     per row the Frobenius norm of the sag's Hessian at the hit -- an upper bound of the second
-    derivative in any direction -- on Newton rows when asked for, else 0)."""
+    derivative in any direction -- on Newton rows when asked for, else 0; cos: (row, |cos
+    incidence|) of every row the ray was bent at)."""
     last = table.num_surfaces - 1 if last is None else last
     P = (lambda v: +mp.mpf(float(v)))
-    x, y, z, L, M, N, inten, opd = (P(v) for v in ray)
+    # (an mpf is taken as it is, rounded to the precision in force: tests/_exact_front.py hands
+    # over rays it generated at that precision)
+    x, y, z, L, M, N, inten, opd = (+v if isinstance(v, mp.mpf) else P(v) for v in ray)
     rows = []
-    info = dict(lost=False, clipped=False, min_cos=1.0, min_snell=1.0, kappa=[])
+    info = dict(lost=False, clipped=False, min_cos=1.0, min_snell=1.0, kappa=[], cos=[])
     for k in range(first, last + 1):
         s, o = table.surfaces[k], table.optics[k, wl]
         if info["lost"]:
@@ -372,8 +375,8 @@ def trace_ray(mp, table, ray, wl=0, first=0, last=None, want_kappa=False):
         nn = mp.sqrt(fx * fx + fy * fy + 1)
         nx, ny, nz = fx / nn, fy / nn, -1 / nn
         dot = L * nx + M * ny + N * nz
-        info["min_cos"] = min(info["min_cos"],
-                              float(abs(dot) / mp.sqrt(L * L + M * M + N * N)))
+        info["cos"].append((k, float(abs(dot) / mp.sqrt(L * L + M * M + N * N))))
+        info["min_cos"] = min(info["min_cos"], info["cos"][-1][1])
         # ---- the mirror law / Snell's law on the normal turned along the ray
         if int(s["interaction"]) == S.INTERACT_REFLECT:
             L, M, N = L - 2 * dot * nx, M - 2 * dot * ny, N - 2 * dot * nz

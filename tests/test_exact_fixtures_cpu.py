@@ -182,3 +182,146 @@ def test_exact_trace_truth_agrees_with_the_oracle():
             f"{grp} {e / s:.1e}" for grp, e, s in zip(X.GROUPS, err, scale)) + f" (tol {tol:g})")
         assert np.all(err <= tol * scale), (name, err / scale)
         assert np.array_equal(np.isnan(ref[:, :, keep]), np.isnan(truth[:, :, keep]))
+
+
+# ---- tests/golden/exact_front.npz (tools/make_golden_exact_front.py, tests/_exact_front.py) ----
+from tests import _exact_front as F  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def gen_front():
+    pytest.importorskip("mpmath")
+    spec = importlib.util.spec_from_file_location(
+        "make_golden_exact_front", os.path.join(ROOT, "tools", "make_golden_exact_front.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_exact_front_fixture_holds_what_the_front_tests_read():
+    g = F.load()
+    assert os.path.getsize(F.GOLD) < 1 << 20
+    assert all(v.dtype.kind in "fib" for v in g.values())     # numbers only
+    floored = 0
+    for name, subs in F.GEN_CASES.items():
+        n = g[f"gen/{name}/pxy"].shape[1]
+        assert g[f"gen/{name}/pxy"].dtype == np.float32 and n >= 132
+        for sub in range(len(subs)):
+            key = f"gen/{name}/{sub}"
+            assert g[f"{key}/truth"].shape == (7, n) and np.isfinite(g[f"{key}/truth"]).all()
+            # the inputs are fp32 numbers: the same inputs for both dtypes
+            assert np.array_equal(F.f32(g[f"{key}/par"][:4]), g[f"{key}/par"][:4])
+            for tag in F.TAGS:
+                yard, scale = g[f"{key}/{tag}/yard"], g[f"{key}/scale"]
+                assert yard.shape == (3,) and np.isfinite(yard).all() and np.all(yard >= 0)
+                # a yardstick below one rounding of the scale is degenerate: the floor applies
+                low = yard < F.EPS[tag] * scale
+                floored += int(low.sum())
+                lim = F.floor_bound(yard, scale, tag)
+                assert np.all(lim[low] == 2 * F.EPS[tag] * scale[low]) and np.all(lim > 0)
+    # the zero-length rule is reached: axial chief rays, and one point on either side of 1e-9
+    z = g[f"gen/{F.ZERO}/0/truth"]
+    assert np.array_equal(z[3:6, [0, -2]], [[0, 0], [0, 0], [1, 1]]) and z[3, -1] == 1.0
+    assert set(g["gen/cooke_generic/probe"][:, 1]) == {0, 8, 16, 24}
+    for name in F.TRACE_CASES:
+        table = F.table_for(name)
+        rows, keep = table.num_surfaces, g[f"trace/{name}/keep"]
+        n = keep.size
+        image = g[f"trace/{name}/image"]
+        assert n == 264 and g[f"trace/{name}/rows"].shape == (rows, 8, n // 2)
+        # the conditions of the sums: no ray is lost, whatever is not clipped is kept ...
+        assert np.isfinite(image).all() and np.array_equal(image[6] > 0, keep)
+        assert n - int(keep.sum()) <= F.X.MAX_DROPPED * n
+        # ... and no truth hit lies closer to an aperture edge than the fp32 position bound
+        b32 = F.trace_bound(g, name, "f32")[:, 0]
+        assert np.all(g[f"trace/{name}/margin"] > b32)
+        for k in range(rows):
+            margin = F.edge_margin(table, g[f"trace/{name}/rows"][k, :2], k)
+            assert margin.min() >= g[f"trace/{name}/margin"][k] > b32[k]
+        # the lever term's inputs: a step over a cosine per bent row, cosines the kept rays have
+        lever, cosmin = g[f"trace/{name}/lever"], g[f"trace/{name}/cosmin"]
+        assert lever.shape == cosmin.shape == (rows,) and np.all(lever >= 0) and lever[-1] > 0
+        assert np.all(cosmin >= F.X.MIN_COS) and np.all(cosmin <= 1)
+        for tag in F.TAGS:
+            yard = g[f"trace/{name}/{tag}/yard"]
+            assert yard.shape == (rows, 4) and np.isfinite(yard).all()
+            # the lever term touches the position alone
+            plain = F.X.bound(yard, g[f"trace/{name}/scale"], tag, F.X.newton_terms(
+                F.table_for(name, tag), tag, g[f"trace/{name}/kappa"]), np.zeros(rows))
+            with_lever = F.trace_bound(g, name, tag)
+            assert np.array_equal(with_lever[:, 2:], plain[:, 2:])
+            assert np.all(with_lever[:, 0] >= plain[:, 0])
+            floored += int((yard < F.EPS[tag] * g[f"trace/{name}/scale"]).sum())
+            assert g[f"spot/{name}/{tag}/moments"][0, 0] == keep.sum()
+            c = g[f"spot/{name}/{tag}/center"][1]
+            assert np.array_equal(c.astype(F.X.NP_DTYPE[tag]).astype(np.float64), c)
+        for f in (0, 1):
+            for kind in F.REFS:
+                key = f"opd/{name}/{f}/{kind}"
+                assert g[f"{key}/opd"].shape == (n // 2,) and np.isfinite(g[f"{key}/opd"]).all()
+                planar = bool(np.any(g[f"{key}/par"][10:13] != 0))
+                assert planar == (kind == "plane")
+                assert g[f"{key}/moments_a"][9] == keep[f * 132:(f + 1) * 132].sum()
+                S_ = g[f"{key}/scales"][0]
+                for path in "abc":
+                    floored += int(g[f"{key}/yard_{path}"][0] < F.EPS["f64"] * S_)
+    # the double Gauss stop clips the off-axis bundle, and only that
+    dg = g["trace/double_gauss/keep"]
+    assert dg[:132].all() and 0 < (~dg[132:]).sum()
+    # one table takes the last step, and one field has tilt cosines
+    assert F.table_for("finite_object_height_telecentric_generic").last_thickness > 0
+    assert g["opd/cooke_generic/1/sphere/par"][6] != 0
+    print(f"\n[exact front] yardsticks below eps x scale (the floor applies): {floored}")
+    assert floored > 0
+
+
+def test_samples_of_every_exact_front_case_are_made_again_bit_for_bit(gen_front):
+    g = F.load()
+    for name in F.GEN_CASES:
+        n = g[f"gen/{name}/pxy"].shape[1]
+        only = [0, 7, n // 2, n - 1]
+        made = gen_front.make_gen(name, only=only)
+        assert made[f"gen/{name}/pxy"].tobytes() == g[f"gen/{name}/pxy"].tobytes()
+        for sub in range(len(F.GEN_CASES[name])):
+            a, b = made[f"gen/{name}/{sub}/truth"][:, only], g[f"gen/{name}/{sub}/truth"][:, only]
+            assert a.tobytes() == b.tobytes(), (name, sub)
+    for name in F.TRACE_CASES:
+        only = [0, 139, 263]
+        made = gen_front.make_trace(name, only=only)
+        assert made[f"trace/{name}/in"].tobytes() == g[f"trace/{name}/in"].tobytes()
+        a, b = made[f"trace/{name}/image"][:, only], g[f"trace/{name}/image"][:, only]
+        assert a.tobytes() == b.tobytes(), name
+        a = made[f"trace/{name}/rows"][:, :, [7, 131]]
+        assert a.tobytes() == g[f"trace/{name}/rows"][:, :, [7, 131]].tobytes(), name
+
+
+def test_exact_front_truth_agrees_with_the_oracle():
+    """The truth's own conventions against the fp64 oracle: generated rays to 1e-12 of their
+    scale, image rows to the tolerances of test_exact_trace_truth_agrees_with_the_oracle."""
+    from oracle import oracle
+    g = F.load()
+    for name, subs in F.GEN_CASES.items():
+        rg = F.table_for(name).raygen
+        px, py = g[f"gen/{name}/pxy"].astype(np.float64)
+        for sub in range(len(subs)):
+            hx, hy, vx, vy, flags = g[f"gen/{name}/{sub}/par"]
+            s = (vx, vy) if int(flags) & F.PRESCALE else (1.0, 1.0)
+            r = oracle.generate_rays(rg, hx, hy, px * s[0], py * s[1],
+                                     np.full(px.size, vx), np.full(px.size, vy))
+            got = np.stack([r[k] for k in ("x", "y", "z", "L", "M", "N", "i")])
+            err = np.abs(got - g[f"gen/{name}/{sub}/truth"])
+            scale = np.repeat(g[f"gen/{name}/{sub}/scale"], [3, 3, 1])[:, None]
+            assert np.all(err <= 1e-12 * scale), (name, sub, (err / scale).max())
+    for name in F.TRACE_CASES:
+        table = F.table_for(name)
+        px, py, hx, hy = g[f"trace/{name}/in"].astype(np.float64)
+        vig, keep = g[f"trace/{name}/vig"], g[f"trace/{name}/keep"]
+        r = oracle.generate_rays(table.raygen, hx, hy, px, py, np.full(px.size, vig[0]),
+                                 np.full(px.size, vig[1]))
+        rec = oracle.trace(table, {k: r[k] for k in ("x", "y", "z", "L", "M", "N", "i")}, 0,
+                           record=True)["record"]
+        newton = np.isin(table.surfaces["geom_kind"], F.X.NEWTON).any()
+        err = F.X.group_max(rec[-1:] - g[f"trace/{name}/image"][None], keep)[0]
+        scale = np.maximum(g[f"trace/{name}/scale"][-1], [0, 1, 0, 0])
+        assert np.all(err <= (1e-7 if newton else 1e-9) * scale), (name, err / scale)
+        assert np.array_equal(rec[-1, 6] > 0, keep)
