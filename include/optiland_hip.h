@@ -792,6 +792,77 @@ int ol_trace_spot_batch(const ol_system* sys, ol_dtype dt, int64_t n_rays,
                         int32_t n_cells, const ol_spot_cell* cells, void* hits,
                         int64_t hits_stride, double* out8, uint32_t* status, void* stream);
 
+/* Additive within ABI 11 (looked up by name, like the one-launch kinds).  ol_trace_spot_batch taken
+ * one step further: K VARIANTS of one optic -- the same structure, other values: what Monte Carlo
+ * tolerancing, a sensitivity table, a finite-difference Jacobian or a population optimiser trace
+ * (tolerancing/monte_carlo.py: one perturbed lens per iteration) -- resident on the device
+ * together, and a grid of (variant, field, wavelength) cells traced and reduced to spot moments in
+ * ONE launch instead of one table upload, one launch and one status read-back per variant.
+ *
+ * ol_ensemble owns, per precision, the four tables of a system STACKED ([K][n_surf] hot rows,
+ * [K][n_surf] cold rows, [K][n_surf][n_wl] optics rows, [K][coeff_cap] coefficients) and one
+ * block of ray-generation constants PER VARIANT: a radius in front of the stop moves the entrance
+ * pupil, so EPL / EPD are values of the variant like any radius.
+ *
+ * Structure: every variant must agree with variant 0 in everything that selects code or layout --
+ * surface and wavelength counts, per surface the geometry, interaction, aperture and coating kind,
+ * the flags (but OL_SURF_ROTATED, which states what rot[] holds), n_coeff, coeff_offset and
+ * poly_cols, the length of the coefficient buffer, and the layout of the staged coefficient
+ * blocks.  A mismatch is OL_EINVAL and names the variant, the surface and the field.  Systems
+ * with one-launch kinds (Forbes, grating, phase, grid sag) and OL_SURF_REFERENCE_NEWTON systems are
+ * refused (OL_EUNSUPPORTED) as ol_trace_spot_batch refuses them.
+ *   ol_ensemble_create   `variants`: K records of HOST memory; nothing is kept of them
+ *   ol_ensemble_update   rewrites variants [k0, k0 + count) IN PLACE from `variants[0 .. count)`:
+ *                        no allocation, the copies are queued on `stream` like ol_system_update's
+ *                        (after every launch queued there that still reads the old rows).  All
+ *                        records are checked before the first copy: a refused update changes
+ *                        nothing                                                              */
+typedef struct ol_ensemble ol_ensemble; /* opaque */
+typedef struct ol_ensemble_variant {
+  const ol_surface_desc* surf;      /* n_surf rows                                          */
+  const double* coeffs;             /* the variant's coefficient buffer                     */
+  const ol_surface_optics* optics;  /* [n_surf][n_wavelengths]                              */
+  const ol_raygen_params* raygen;   /* the variant's OWN ray-generation scalars             */
+  int32_t n_coeffs;
+  int32_t reserved_;
+} ol_ensemble_variant;
+int ol_ensemble_create(const ol_ensemble_variant* variants, int32_t n_variants, int32_t n_surf,
+                       int32_t n_wavelengths, ol_ensemble** out);
+int ol_ensemble_update(ol_ensemble* ens, int32_t k0, int32_t count,
+                       const ol_ensemble_variant* variants, void* stream);
+void ol_ensemble_destroy(ol_ensemble* ens);
+int32_t ol_ensemble_size(const ol_ensemble* ens);
+
+/* One cell of an ensemble launch, DEVICE memory (there may be far more cells than a kernel
+ * argument holds): the variant it traces, its wavelength row, field point, vignetting factors and
+ * the centre its moments are taken about -- per cell what ol_spot_cell carries.  The field
+ * tangents are formed on the device from the VARIANT's constants, as for per-ray field planes.  */
+typedef struct ol_ensemble_cell {
+  int32_t variant;
+  int32_t wavelength_index;
+  double hx, hy;            /* normalised field of the cell                               */
+  double vx, vy;            /* 1 - vignetting factor at that field                        */
+  double cx, cy;            /* centre the moments are taken about                         */
+} ol_ensemble_cell;
+#define OL_STATUS_ENSEMBLE_CELL 0x40u /* a cell names a variant or a wavelength row the ensemble
+                                         does not hold: the cell is skipped (nothing of it is
+                                         read, traced or written)                               */
+/*   in        px, py planes and flags only, as for ol_trace_spot_batch (OL_RAYGEN_CHECK_FIELD
+ *             checks the cells' fields where the kernel reads them: OL_STATUS_FIELD_RANGE)
+ *   cells_dev n_cells records (at most 65535 x 65535); cell c is workgroup-uniform: the kernel
+ *             takes it from blockIdx.y and blockIdx.z
+ *   hits      NULL, or ONE block of n_cells x 3 planes (x, y, intensity of cell c at
+ *             hits + (3 c + k) hits_stride elements), hits_stride >= n_rays
+ *   out8      n_cells x 8 DEVICE doubles, ACCUMULATED (zero them first): per cell the seven
+ *             of ol_trace_spot, element 7 unused
+ *   status    required (a cell is validated on the device)
+ * OL_SPOT_POLARIZED_OK and OL_SPOT_HITS_LOCAL as for ol_trace_spot_batch.  Every variant's hits
+ * are those of ol_trace_spot on an ol_system of that variant alone, bit for bit.             */
+int ol_trace_spot_ensemble(const ol_ensemble* ens, ol_dtype dt, int64_t n_rays,
+                           const ol_raygen_inputs* in, int64_t n_cells,
+                           const ol_ensemble_cell* cells_dev, void* hits, int64_t hits_stride,
+                           double* out8, uint32_t* status, void* stream);
+
 /* Wavefront OPD against a spherical reference centred on the chief-ray image point
  * (wavefront/strategy.py:163-215 ChiefRayStrategy.
  * compute_wavefront_data, wavefront/reference_geometry.py:41-79

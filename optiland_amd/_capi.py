@@ -159,6 +159,11 @@ EXPORTS = (
     "ol_trace_grating",
     "ol_trace_phase",
     "ol_trace_grid_sag",
+    "ol_ensemble_create",
+    "ol_ensemble_update",
+    "ol_ensemble_destroy",
+    "ol_ensemble_size",
+    "ol_trace_spot_ensemble",
 )
 
 F32, F64 = 0, 1
@@ -319,7 +324,42 @@ def bind(lib, path: str = "?"):
             entry.restype = C.c_int
             entry.argtypes = [vp, C.c_int, i64, C.POINTER(vp), i32] \
                 + ([C.c_double] if kind.wavelength else []) + [vp, i64, i32, u32, vp, vp]
+    if has_ensemble(lib):   # (additive within ABI 11: the five come together)
+        lib.ol_ensemble_create.restype = C.c_int
+        lib.ol_ensemble_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
+        lib.ol_ensemble_update.restype = C.c_int
+        lib.ol_ensemble_update.argtypes = [vp, i32, i32, vp, vp]
+        lib.ol_ensemble_destroy.restype = None
+        lib.ol_ensemble_destroy.argtypes = [vp]
+        lib.ol_ensemble_size.restype = i32
+        lib.ol_ensemble_size.argtypes = [vp]
+        lib.ol_trace_spot_ensemble.restype = C.c_int
+        lib.ol_trace_spot_ensemble.argtypes = [vp, C.c_int, i64, vp, i64, vp, vp, i64, vp, vp, vp]
     return lib
+
+
+STATUS_ENSEMBLE_CELL = 0x40   # OL_STATUS_ENSEMBLE_CELL
+
+
+class EnsembleVariant(C.Structure):
+    """ol_ensemble_variant"""
+    _fields_ = [("surf", C.c_void_p), ("coeffs", C.c_void_p), ("optics", C.c_void_p),
+                ("raygen", C.c_void_p), ("n_coeffs", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class EnsembleCell(C.Structure):
+    """ol_ensemble_cell"""
+    _fields_ = [("variant", C.c_int32), ("wavelength_index", C.c_int32), ("hx", C.c_double),
+                ("hy", C.c_double), ("vx", C.c_double), ("vy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double)]
+
+
+def has_ensemble(lib) -> bool:
+    """True when the loaded library exports the ol_ensemble_* entries and
+    ol_trace_spot_ensemble."""
+    return all(hasattr(lib, s) for s in ("ol_ensemble_create", "ol_ensemble_update",
+                                         "ol_ensemble_destroy", "ol_ensemble_size",
+                                         "ol_trace_spot_ensemble"))
 
 
 # OL_ZK_* / OL_SMTF_* (optiland_hip.h)

@@ -23,6 +23,7 @@
 #include "last_error.h"
 #include "system_stage.h"
 #include "system_view.h"
+#include "table_image.h"
 #include "trace_launch.h"
 
 namespace {
@@ -102,34 +103,7 @@ int upload(const std::vector<HostSurf>& surf64,
   auto* cold = reinterpret_cast<ol::DevSurfCold<T>*>(host.data() + off_cold);
   auto* opt = reinterpret_cast<ol::DevOptics<T>*>(host.data() + off_opt);
   T* coef = reinterpret_cast<T*>(host.data() + off_coef);
-  for (size_t i = 0; i < n_surf; ++i) {
-    const auto& a = surf64[i];
-    auto& b = surf[i];
-    auto& c = cold[i];
-    b.geom = a.geom; b.interaction = a.interaction; b.aperture_kind = a.aperture_kind;
-    b.coating_kind = a.coating_kind; b.coeff_off = a.coeff_off; b.n_coeff = a.n_coeff;
-    b.max_iter = a.max_iter; b.flags = a.flags;
-    b.cv = (T)a.cv; b.kp1 = (T)a.kp1;
-    c.poly_cols = a.poly_cols; c.coeff_len = a.coeff_len; c.ap_off = a.ap_off;
-    c.ap_len = a.ap_len; c.tol = (T)a.tol; c.inv_norm = (T)a.inv_norm;
-    for (int k = 0; k < 3; ++k) { b.origin[k] = (T)a.origin[k]; b.rel_off[k] = (T)a.rel_off[k]; }
-    for (int k = 0; k < 9; ++k) { c.rot[k] = (T)a.rot[k]; c.rel_rot[k] = (T)a.rel_rot[k]; }
-    for (int k = 0; k < 4; ++k) c.ap[k] = (T)a.ap[k];
-    for (int k = 0; k < 2; ++k) c.coat[k] = (T)a.coat[k];
-    for (int k = 0; k < 3; ++k) c.axis[k] = (T)a.axis[k];
-    c.ret_cos = (T)a.ret_cos; c.ret_sin = (T)a.ret_sin;
-    c.radius = (T)a.radius; c.conic = (T)a.conic;
-  }
-  for (size_t i = 0; i < n_opt; ++i) {
-    opt[i].n1 = (T)opt64[i].n1; opt[i].n2 = (T)opt64[i].n2; opt[i].u = (T)opt64[i].u;
-    opt[i].nn = (T)opt64[i].nn; opt[i].absorb = (T)opt64[i].absorb;
-  }
-  for (size_t i = 0; i < coef64.size(); ++i) coef[i] = (T)coef64[i];
-  for (size_t i : int_slots) {  // loop headers: integer bit patterns (scalar-unit operands)
-    using I = typename std::conditional<sizeof(T) == 4, int32_t, int64_t>::type;
-    const I v = (I)coef64[i];
-    std::memcpy(&coef[i], &v, sizeof(T));
-  }
+  ol::write_table_image<T>(surf64, opt64, coef64, int_slots, surf, cold, opt, coef);
 
   if (in_place) {
     // same surface / wavelength counts (checked by the caller): the block offsets are the
@@ -161,35 +135,9 @@ void release(DeviceTable<T>& t) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// Which Newton kernel a traced range needs (trace_launch.h: launch_trace): 0 = none,
-// 3 / 4 = all of its Newton-Raphson surfaces are Zernike surfaces / even aspheres, 5 = the
-// reference's batch-global stop rule was asked for (OL_SURF_REFERENCE_NEWTON), else 1.
-// (A polygon aperture on a conic-only range also selects the generic kernel: polygons live
-// in the full kernels only.)
+// the Newton kernel family of a traced range (system_stage.h: newton_family_of)
 int newton_family(const ol_system* sys, int32_t first, int32_t last) {
-  bool any = false, polygon = false, all_zernike = true, all_even = true;
-  // OL_SURF_REFERENCE_NEWTON (opt-in, ABI 11) on any Newton surface of the range: the kernel
-  // family that iterates the batch in lockstep (surface_math.h: newton_reference)
-  for (int32_t s = first; s <= last; ++s)
-    if (sys->facts.ref_newton[s]) return ol::kNrReference;
-  for (int32_t s = first; s <= last; ++s) {
-    polygon = polygon || sys->facts.polygon[s];
-    const int g = sys->facts.geom[s];
-    if (g == OL_GEOM_PLANE || g == OL_GEOM_STANDARD) continue;
-    any = true;
-    all_zernike = all_zernike && g == OL_GEOM_ZERNIKE;
-    all_even = all_even && g == OL_GEOM_EVEN_ASPHERE;
-  }
-  if (!any) return polygon ? 1 : 0;
-  // OPTILAND_HIP_NR_FAMILY=0: always the generic Newton kernel (A/B runs; parity tests of the
-  // generic instantiation on single-family systems)
-  static const bool families = [] {
-    const char* e = getenv("OPTILAND_HIP_NR_FAMILY");
-    return !(e && e[0] == '0');
-  }();
-  if (families && all_zernike) return 3;
-  if (families && all_even) return 4;
-  return 1;
+  return newton_family_of(sys->facts, first, last);
 }
 
 template <typename T>

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -544,6 +545,37 @@ inline void stage_facts(const StageIn& in, int32_t n_surf, const std::vector<Hos
                                    s.interaction != OL_INTERACT_RECORD_ONLY
                                ? 1 : 0);
   }
+}
+
+// Which Newton kernel a traced range needs (trace_launch.h: launch_trace): 0 = none,
+// 3 / 4 = all of its Newton-Raphson surfaces are Zernike surfaces / even aspheres, 5 = the
+// reference's batch-global stop rule was asked for (OL_SURF_REFERENCE_NEWTON), else 1.
+// (A polygon aperture on a conic-only range also selects the generic kernel: polygons live
+// in the full kernels only.)
+inline int newton_family_of(const HostFacts& f, int32_t first, int32_t last) {
+  bool any = false, polygon = false, all_zernike = true, all_even = true;
+  // OL_SURF_REFERENCE_NEWTON (opt-in, ABI 11) on any Newton surface of the range: the kernel
+  // family that iterates the batch in lockstep (surface_math.h: newton_reference)
+  for (int32_t s = first; s <= last; ++s)
+    if (f.ref_newton[s]) return kNrReference;
+  for (int32_t s = first; s <= last; ++s) {
+    polygon = polygon || f.polygon[s];
+    const int g = f.geom[s];
+    if (g == OL_GEOM_PLANE || g == OL_GEOM_STANDARD) continue;
+    any = true;
+    all_zernike = all_zernike && g == OL_GEOM_ZERNIKE;
+    all_even = all_even && g == OL_GEOM_EVEN_ASPHERE;
+  }
+  if (!any) return polygon ? 1 : 0;
+  // OPTILAND_HIP_NR_FAMILY=0: always the generic Newton kernel (A/B runs; parity tests of the
+  // generic instantiation on single-family systems)
+  static const bool families = [] {
+    const char* e = getenv("OPTILAND_HIP_NR_FAMILY");
+    return !(e && e[0] == '0');
+  }();
+  if (families && all_zernike) return 3;
+  if (families && all_even) return 4;
+  return 1;
 }
 
 // argument validation + every host-side conversion of ol_system_create / ol_system_update

@@ -1209,3 +1209,40 @@ def _host_first_order(optic, table: SystemTable, pos, infinite, tokens=None, cac
     if fo is not None:
         fo["n_image"] = n[-1]
     return fo
+
+
+def pack_ensemble(optic, mutate, K: int, wavelengths=None, restore=None) -> list:
+    """K packed variants of `optic`: for k = 0 .. K - 1, `mutate(optic, k)` then `pack_optic`
+    (what `ensemble.SystemEnsemble` is built from).  The packs go through the change detector's
+    tokens and one per-surface cache, so a surface `mutate` left alone since the previous variant
+    is not read again.
+
+    `restore`: None -- `mutate` is handed a deep copy of `optic`, which itself is never touched
+    (`mutate` must act on the optic it is HANDED); or a callable `restore(optic)` that undoes every
+    mutation (a tolerancing problem's `reset`): the variants are then made on `optic` itself and
+    `restore` runs afterwards whatever happened."""
+    import copy
+
+    from . import fingerprint as _fp
+
+    if wavelengths is None:
+        wavelengths = [_f(w.value) for w in optic.wavelengths.wavelengths]
+    wavelengths = [float(w) for w in wavelengths]
+    work = copy.deepcopy(optic) if restore is None else optic
+    cache: dict = {}
+
+    def pack():
+        if _fp.ENABLED:
+            tok, keep = _fp.optic_token(work, wavelengths[0])
+            return pack_optic(work, wavelengths, tokens=tok[1], cache=cache, keep=keep)
+        return pack_optic(work, wavelengths)
+
+    tables = []
+    try:
+        for k in range(int(K)):
+            mutate(work, k)
+            tables.append(pack())
+    finally:
+        if restore is not None:
+            restore(work)
+    return tables
