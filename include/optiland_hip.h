@@ -950,6 +950,55 @@ int ol_trace_opd_dev(const ol_system* sys, ol_dtype dt, int64_t n_rays,
                      void* intensity, void* const pupil[3], double* moments12, uint32_t* status,
                      void* stream);
 
+/* Additive within ABI 11 (looked up by name, like ol_trace_spot_ensemble).  The wavefronts of an
+ * ensemble: for every (variant, field, wavelength) cell what ol_wavefront_reference +
+ * ol_trace_opd_dev compute on an ol_system of that variant alone -- the chief ray's reference
+ * sphere / plane, the OPD map against it and its twelve moments -- in TWO launches for all cells
+ * (one lane per cell for the chief rays, then the maps), queued on `stream` with no read-back
+ * between them.  What Monte Carlo tolerancing of a wavefront merit traces
+ * (optimization/operand/ray.py:343-389 OPD_difference: one Wavefront per operand and iteration).
+ *
+ * One cell, DEVICE memory like ol_ensemble_cell.  An ensemble stores the ray-generation scalars of
+ * its variants but not their exit pupils or image-space indices, so the CELL carries what
+ * ol_wavefront_reference is handed per call; the launch-plane tilt (ux, uy) and half_epd are
+ * formed on the device from the variant's own constants.                                       */
+typedef struct ol_ensemble_opd_cell {
+  int32_t variant;
+  int32_t wavelength_index;
+  double hx, hy;            /* normalised field of the cell                               */
+  double vx, vy;            /* 1 - vignetting factor at that field                        */
+  double n_image;           /* the VARIANT's image-space index at the primary wavelength  */
+  double pupil_z;           /* the VARIANT's exit-pupil position (spherical reference)    */
+  double wavelength_um;
+  double last_thickness;    /* ol_wavefront_params.last_thickness                         */
+  int32_t planar;           /* != 0: afocal, the plane through the chief ray's hit        */
+  int32_t reserved_;
+} ol_ensemble_opd_cell;
+#define OL_OPD_ENSEMBLE_PUPIL 0x100u /* in->flags: planes holds 5 planes per cell, not 2 */
+/*   in        px, py planes and flags only, as for ol_trace_spot_ensemble
+ *   cells_dev n_cells records (at most 65535 x 65535); a cell that names a variant or a
+ *             wavelength row the ensemble does not hold raises OL_STATUS_ENSEMBLE_CELL in both
+ *             launches and nothing of it is read, traced or written
+ *   refs      n_cells x OL_WAVEFRONT_REFERENCE_DOUBLES DEVICE doubles, WRITTEN: per cell the
+ *             structure ol_wavefront_reference leaves ([0..2] centre, [3] radius).  An output
+ *             too: centre, radius and opd_ref of every cell
+ *   planes    NULL, or ONE block of n_cells x P planes, P = 2: the OPD in waves and the
+ *             image-plane intensity; P = 5 with OL_OPD_ENSEMBLE_PUPIL: + the three pupil-point
+ *             planes.  Plane k of cell c at planes + (P c + k) planes_stride elements,
+ *             planes_stride >= n_rays
+ *   moments12 n_cells x 12 DEVICE doubles, ACCUMULATED (zero them first): per cell the twelve
+ *             of ol_trace_opd
+ *   status    required (a cell is validated on the device)
+ * fp64 only (OL_F32 -> OL_EUNSUPPORTED); polarization-dependent coatings are refused as by
+ * ol_trace_opd.  Nothing is launched for n_rays == 0 or n_cells == 0.  On-axis cells (field
+ * tangents exactly 0) equal the two single launches bit for bit; off axis the tangents and the
+ * tilt come from the device's tan() instead of the host's.                                    */
+int ol_trace_opd_ensemble(const ol_ensemble* ens, ol_dtype dt, int64_t n_rays,
+                          const ol_raygen_inputs* in, int64_t n_cells,
+                          const ol_ensemble_opd_cell* cells_dev, void* refs, void* planes,
+                          int64_t planes_stride, double* moments12, uint32_t* status,
+                          void* stream);
+
 /* ABI 9.  The FITTED reference of a wavefront, device-resident: what CentroidStrategy and
  * BestFitStrategy (wavefront/strategy.py:287-620) derive from the traced bundle -- the sphere
  * centred on the intensity-weighted (optionally k-sigma trimmed) centroid of the image points

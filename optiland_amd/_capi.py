@@ -164,6 +164,7 @@ EXPORTS = (
     "ol_ensemble_destroy",
     "ol_ensemble_size",
     "ol_trace_spot_ensemble",
+    "ol_trace_opd_ensemble",
 )
 
 F32, F64 = 0, 1
@@ -335,6 +336,10 @@ def bind(lib, path: str = "?"):
         lib.ol_ensemble_size.argtypes = [vp]
         lib.ol_trace_spot_ensemble.restype = C.c_int
         lib.ol_trace_spot_ensemble.argtypes = [vp, C.c_int, i64, vp, i64, vp, vp, i64, vp, vp, vp]
+    if has_ensemble_opd(lib):   # (additive within ABI 11)
+        lib.ol_trace_opd_ensemble.restype = C.c_int
+        lib.ol_trace_opd_ensemble.argtypes = [vp, C.c_int, i64, vp, i64, vp, vp, vp, i64, vp, vp,
+                                              vp]
     return lib
 
 
@@ -352,6 +357,22 @@ class EnsembleCell(C.Structure):
     _fields_ = [("variant", C.c_int32), ("wavelength_index", C.c_int32), ("hx", C.c_double),
                 ("hy", C.c_double), ("vx", C.c_double), ("vy", C.c_double), ("cx", C.c_double),
                 ("cy", C.c_double)]
+
+
+class EnsembleOpdCell(C.Structure):
+    """ol_ensemble_opd_cell"""
+    _fields_ = [("variant", C.c_int32), ("wavelength_index", C.c_int32), ("hx", C.c_double),
+                ("hy", C.c_double), ("vx", C.c_double), ("vy", C.c_double),
+                ("n_image", C.c_double), ("pupil_z", C.c_double), ("wavelength_um", C.c_double),
+                ("last_thickness", C.c_double), ("planar", C.c_int32), ("reserved_", C.c_int32)]
+
+
+OPD_ENSEMBLE_PUPIL = 0x100   # OL_OPD_ENSEMBLE_PUPIL
+
+
+def has_ensemble_opd(lib) -> bool:
+    """True when the loaded library serves ensembles and exports ol_trace_opd_ensemble."""
+    return has_ensemble(lib) and hasattr(lib, "ol_trace_opd_ensemble")
 
 
 def has_ensemble(lib) -> bool:

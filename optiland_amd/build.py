@@ -19,7 +19,7 @@ LIBNAME = "liboptiland_hip.so"
 # translation units -- so that the two halves (the bulk of the build) run in parallel
 SOURCES = ("trace_kernel_f32.hip", "trace_kernel_f64.hip", "aux_kernels.hip", "capi.hip",
            "huygens.hip", "mtf.hip", "zernike_fit.hip", "mmdft.hip", "ray_aim.hip", "forbes.hip",
-           "grating.hip", "phase.hip", "grid_sag.hip", "ensemble.hip")
+           "grating.hip", "phase.hip", "grid_sag.hip", "ensemble.hip", "ensemble_opd.hip")
 # every header under csrc/ (round 5: a hand-kept list had missed wavefront_fit_device.h since
 # round 4 -- an edit of that file alone left a stale aux_kernels.o behind) + the included .hip
 HEADERS = tuple(sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))) + ("trace_kernel.hip",)

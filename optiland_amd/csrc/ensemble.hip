@@ -27,6 +27,7 @@
 #include "../../include/optiland_hip.h"
 #include "ensemble_device.h"
 #include "ensemble_rules.h"
+#include "ensemble_store.h"   // struct ol_ensemble
 #include "entry_rules.h"
 #include "last_error.h"
 #include "system_stage.h"
@@ -197,13 +198,6 @@ hipError_t launch_ensemble(const EnsembleArgs<T>& a, bool vector_ok, int nr_fami
 inline size_t round256(size_t v) { return (v + 255u) & ~size_t(255u); }
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// the stacked tables of one precision: ONE allocation, each table on a 256-byte boundary
-template <typename T>
-struct EnsembleStore {
-  char* blob = nullptr;
-  EnsembleTables<T> dev{};
-};
-
 template <typename T>
 void release(EnsembleStore<T>& s) {
   if (s.blob) (void)hipFree(s.blob);
@@ -216,43 +210,10 @@ RaygenDev raygen_of(const ol_raygen_params& g) {
                    g.apod_kind};
 }
 
-// the host image of consecutive variants, table by table: what the copies of an upload read
-template <typename T>
-struct RangeImage {
-  std::vector<DevSurfHot<T>> surf;
-  std::vector<DevSurfCold<T>> cold;
-  std::vector<DevOptics<T>> optics;
-  std::vector<T> coeffs;
-  std::vector<RaygenConsts<T>> rgc;
-};
-
 }  // namespace
 }  // namespace ol
 
 using namespace ol;
-
-struct ol_ensemble {
-  int32_t n_variants = 0, n_surf = 0, n_wl = 0;
-  int device = 0;
-  size_t coef_cap = 1;
-  int family = 0;                        // Newton kernel family of the shared structure
-  bool apod = false;
-  // variant 0 as created: what every later variant is held against
-  std::vector<ol_surface_desc> ref_rows;
-  int32_t ref_coeffs = 0;
-  ol_raygen_params ref_raygen{};
-  Staged ref;
-  EnsembleStore<float> f32;
-  EnsembleStore<double> f64;
-  bool consistent = true;   // false between the two uploads of an update, for good if one fails
-  // The sources of the queued copies.  They are pageable memory, megabytes of it at thousands of
-  // variants, and nothing here leans on when the runtime has finished reading such a source: the
-  // images live in the ensemble, `copied` is recorded behind the copies, and the next update
-  // (or the destruction) waits for it before the images are written again (or freed).
-  RangeImage<float> image32;
-  RangeImage<double> image64;
-  hipEvent_t copied = nullptr;
-};
 
 namespace {
 

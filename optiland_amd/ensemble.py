@@ -9,6 +9,11 @@ their STRUCTURE and differ in values); `trace_spot` traces any grid of (variant,
 wavelength) cells over one set of pupil points in one launch and reads the status word back once.
 `EnsembleSpot` is the stand-alone analysis on top: centroid, RMS and geometric spot radius as
 (K, F, W) arrays, with `analysis.SpotDiagram`'s definitions.
+
+`trace_opd` (`ol_trace_opd_ensemble`) does the same for wavefronts: every cell's chief-ray
+reference, OPD map and the twelve moments of `ol_trace_opd` in two launches for all cells;
+`EnsembleWavefront` is the analysis on top (RMS, mean and reference radius as (K, F, W) arrays,
+with `wavefront.OPD`'s definitions).
 """
 
 from __future__ import annotations
@@ -138,6 +143,52 @@ CELL_DTYPE = np.dtype([("variant", np.int32), ("wavelength_index", np.int32), ("
                        ("hy", np.float64), ("vx", np.float64), ("vy", np.float64),
                        ("cx", np.float64), ("cy", np.float64)], align=True)
 assert CELL_DTYPE.itemsize == C.sizeof(_capi.EnsembleCell)
+
+OPD_CELL_DTYPE = np.dtype([("variant", np.int32), ("wavelength_index", np.int32),
+                           ("hx", np.float64), ("hy", np.float64), ("vx", np.float64),
+                           ("vy", np.float64), ("n_image", np.float64), ("pupil_z", np.float64),
+                           ("wavelength_um", np.float64), ("last_thickness", np.float64),
+                           ("planar", np.int32), ("reserved_", np.int32)], align=True)
+assert OPD_CELL_DTYPE.itemsize == C.sizeof(_capi.EnsembleOpdCell)
+
+
+def opd_cell_grid(tables, fields, wavelength_indices, vig=None, planar: bool = False) -> np.ndarray:
+    """The (K, F, W) grid of wavefront cells (`_capi.EnsembleOpdCell` layout), ordered like
+    `cell_grid`.  What the ensemble does not store is taken from EACH variant's own table: the
+    image-space index and the exit-pupil position of its `raygen`, its last thickness; the
+    wavelength in microns is the table's at that row.  `planar`: afocal, every cell against the
+    plane through its chief ray's hit."""
+    tables = list(tables)
+    f = np.asarray(fields, dtype=np.float64).reshape(-1, 2)
+    wl = np.asarray(wavelength_indices, dtype=np.int32).reshape(-1)
+    K, F, W = len(tables), f.shape[0], wl.shape[0]
+    cells = np.zeros((K, F, W), dtype=OPD_CELL_DTYPE)
+    cells["variant"] = np.arange(K, dtype=np.int32)[:, None, None]
+    cells["wavelength_index"] = wl[None, None, :]
+    cells["hx"] = f[None, :, 0, None]
+    cells["hy"] = f[None, :, 1, None]
+    v = np.ones((F, 2)) if vig is None else np.asarray(vig, dtype=np.float64).reshape(F, 2)
+    cells["vx"] = v[None, :, 0, None]
+    cells["vy"] = v[None, :, 1, None]
+    cells["planar"] = 1 if planar else 0
+    for k, t in enumerate(tables):
+        rg = t.raygen
+        if "pupil_z" not in rg or "n_image" not in rg:
+            raise ValueError("this SystemTable carries no exit-pupil data")
+        cells["n_image"][k] = float(rg["n_image"])
+        cells["pupil_z"][k] = float(rg["pupil_z"])
+        cells["last_thickness"][k] = float(t.last_thickness)
+        cells["wavelength_um"][k] = np.asarray(t.wavelengths, dtype=np.float64)[wl][None, :]
+    return cells
+
+
+def opd_statistics(moments) -> tuple:
+    """(RMS, mean) of the OPD in waves over the rays that arrive, from (..., 12) moments, with
+    `wavefront.OPD`'s definitions: RMS = sqrt(sum o^2 / count) (opd.py:145-159), mean =
+    sum o / count.  A cell without a surviving ray gives NaN."""
+    m = np.asarray(moments, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.sqrt(m[..., 11] / m[..., 9]), m[..., 10] / m[..., 9]
 
 
 def radii_from_moments(moments) -> tuple:
@@ -298,6 +349,84 @@ class SystemEnsemble:
             self.raise_for_status(int(self._status.item()))
         return out, hb
 
+    def trace_opd(self, px, py, cells, planes=False, pupil: bool = False,
+                  check_status: bool = True, out=None, refs=None, stride: int | None = None,
+                  flags: int = 0):
+        """`ol_trace_opd_ensemble`: every cell of `cells` -- an `opd_cell_grid` array (any shape),
+        or a device uint8 tensor already holding such records -- gets its chief-ray reference
+        and the OPD of the pupil planes `px`, `py` against it: TWO launches for all cells, no
+        read-back between them.  Returns (moments, refs, planes): moments a (cells, 12) float64
+        device tensor (the twelve of `ol_trace_opd`; `out`, if given, is accumulated into), refs
+        (cells, 16) (`[:, 0:3]` centre, `[:, 3]` radius; `refs`, if given, is written), planes
+        None or a (cells, P, stride) block -- P = 2: OPD in waves and intensity, P = 5 with
+        `pupil`: + the pupil point (use `[..., :n]`); a tensor passed as `planes` is written in
+        place.  fp64 ensembles only.  The status word is read back once."""
+        import torch
+        if getattr(self, "_handle", None) is None:
+            raise _capi.HipExtensionError("trace_opd: this ensemble is closed")
+        if not _capi.has_ensemble_opd(self.lib):
+            raise _capi.HipExtensionError("this library has no ol_trace_opd_ensemble: rebuild")
+        if self.dtype != torch.float64:
+            raise ValueError("trace_opd: wavefront work is fp64 only (an fp64 ensemble)")
+        n = int(px.numel())
+        if px.dtype != torch.float64 or py.dtype != torch.float64 or py.numel() != n \
+                or px.device != self.device or py.device != self.device:
+            raise ValueError("trace_opd: px, py must be float64 planes on the ensemble's device, "
+                             "equally long")
+        size = OPD_CELL_DTYPE.itemsize
+        if isinstance(cells, torch.Tensor):
+            if cells.dtype != torch.uint8 or cells.device != self.device \
+                    or cells.numel() % size or not cells.is_contiguous():
+                raise ValueError("trace_opd: device cells must be a contiguous uint8 tensor of "
+                                 "whole ol_ensemble_opd_cell records on the ensemble's device")
+            cells_dev = cells
+        else:
+            host = np.ascontiguousarray(np.asarray(cells, dtype=OPD_CELL_DTYPE).reshape(-1))
+            cells_dev = torch.from_numpy(host.view(np.uint8)).to(self.device)
+        k = cells_dev.numel() // size
+        nref, P = _capi.WAVEFRONT_REFERENCE_DOUBLES, 5 if pupil else 2
+
+        def block(t, shape, what, fresh):
+            if t is None:
+                return fresh(shape, dtype=torch.float64, device=self.device)
+            if tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous() \
+                    or t.device != self.device:
+                raise ValueError(f"{what} must be a contiguous {shape} float64 tensor on the "
+                                 f"device")
+            return t
+
+        out = block(out, (k, _capi.OPD_MOMENTS), "out", torch.zeros)
+        refs = block(refs, (k, nref), "refs", torch.zeros)
+        pb = None
+        if isinstance(planes, torch.Tensor):
+            stride = int(planes.shape[-1]) if planes.dim() == 3 else -1
+            pb = block(planes, (k, P, stride), "planes", torch.empty)
+            if stride < n:
+                raise ValueError(f"planes: stride {stride} < {n} rays")
+        elif planes:
+            stride = max(n if stride is None else int(stride), 1)
+            if stride < n:
+                raise ValueError(f"planes: stride {stride} < {n} rays")
+            pb = torch.empty((k, P, stride), dtype=torch.float64, device=self.device)
+        if n == 0 or k == 0:
+            return out, refs, pb
+        px, py = px.contiguous(), py.contiguous()
+        inp = _capi.RaygenInputs(None, None, px.data_ptr(), py.data_ptr(), None, None, 0.0, 0.0,
+                                 1.0, 1.0, int(flags) | (_capi.OPD_ENSEMBLE_PUPIL if pupil else 0),
+                                 0)
+        if check_status:
+            self._status.zero_()
+        with torch.cuda.device(self.device):
+            rc = self.lib.ol_trace_opd_ensemble(
+                self._handle, _capi.F64, n, C.byref(inp), k, cells_dev.data_ptr(),
+                refs.data_ptr(), pb.data_ptr() if pb is not None else None,
+                stride if pb is not None else 0, out.data_ptr(), self._status.data_ptr(),
+                self._stream())
+        _capi.check(rc, "ol_trace_opd_ensemble", self.lib)
+        if check_status:
+            self.raise_for_status(int(self._status.item()))
+        return out, refs, pb
+
     @staticmethod
     def raise_for_status(status: int) -> None:
         if status & _capi.STATUS_ENSEMBLE_CELL:
@@ -382,3 +511,58 @@ class EnsembleSpot:
     def geometric_spot_radius(self) -> np.ndarray:
         """(K, F, W): max sqrt((x - cx)^2 + (y - cy)^2) about the centres."""
         return radii_from_moments(self.moments)[3]
+
+
+class EnsembleWavefront:
+    """OPD statistics of every variant of an ensemble against its own chief-ray reference: TWO
+    launches for all K x F x W cells.
+
+    `fields`, `wavelengths`: as `EnsembleSpot`; `num_rays`, `distribution`: as `wavefront.OPD`
+    (hexapolar: rings).  `maps`: keep the per-ray planes -- `.opd` and `.intensity` are then
+    (K, F, W, N) arrays (None otherwise).  `planar`: afocal, plane references.  `vig`: F pairs
+    (1 - vx, 1 - vy) (default unvignetted)."""
+
+    def __init__(self, ensemble: SystemEnsemble, fields="all", wavelengths="all",
+                 num_rays: int = 6, distribution: str = "hexapolar", maps: bool = False,
+                 planar: bool = False, vig=None):
+        import torch
+        self.ensemble = ensemble
+        table = ensemble.tables[0]
+        mf = table.raygen.get("max_field", 0.0) or 1.0
+        if isinstance(fields, str) and fields == "all":
+            fields = [(f[0] / mf, f[1] / mf) for f in table.fields]
+        self.fields = [tuple(map(float, f[:2])) for f in fields]
+        if isinstance(wavelengths, str) and wavelengths == "all":
+            wavelengths = list(map(float, table.wavelengths))
+        self.wavelengths = [float(w) for w in wavelengths]
+        self.wl_index = [table.wavelength_index(w) for w in self.wavelengths]
+        K, F, W = len(ensemble), len(self.fields), len(self.wavelengths)
+        x, y = pupil_points(distribution, num_rays)
+        px = torch.from_numpy(x).to(device=ensemble.device, dtype=torch.float64)
+        py = torch.from_numpy(y).to(device=ensemble.device, dtype=torch.float64)
+        self.num_points = n = int(px.numel())
+        self.cells = opd_cell_grid(ensemble.tables, self.fields, self.wl_index, vig=vig,
+                                   planar=planar)
+        mom, refs, pb = ensemble.trace_opd(px, py, self.cells, planes=maps)
+        self.moments = mom.cpu().numpy().reshape(K, F, W, _capi.OPD_MOMENTS)
+        self.references = refs.cpu().numpy().reshape(K, F, W, -1)
+        self.planar = bool(planar)
+        self.opd = self.intensity = None
+        if maps:
+            host = pb[..., :n].cpu().numpy().reshape(K, F, W, 2, n)
+            self.opd, self.intensity = host[..., 0, :], host[..., 1, :]
+
+    def rms(self) -> np.ndarray:
+        """(K, F, W): sqrt(mean(opd^2)) in waves over the rays that arrive (`OPD.rms`)."""
+        return opd_statistics(self.moments)[0]
+
+    def mean(self) -> np.ndarray:
+        """(K, F, W): mean OPD in waves over the rays that arrive."""
+        return opd_statistics(self.moments)[1]
+
+    @property
+    def radius(self) -> np.ndarray:
+        """(K, F, W): radius of every cell's reference sphere in mm (inf for plane references)."""
+        if self.planar:
+            return np.full(self.moments.shape[:3], np.inf)
+        return self.references[..., 3]

@@ -22,7 +22,7 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "optiland_amd", "csrc")
 SOURCES = ("trace_kernel_f32.hip", "trace_kernel_f64.hip", "aux_kernels.hip", "forbes.hip",
-           "grating.hip", "phase.hip", "grid_sag.hip", "ensemble.hip")
+           "grating.hip", "phase.hip", "grid_sag.hip", "ensemble.hip", "ensemble_opd.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on",
          "-fno-math-errno", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
 KEYS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]",
